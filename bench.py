@@ -1,6 +1,6 @@
 """bench.py — training images/sec, SD1.5 LoRA (rank 8) 512px bs=4/GPU, bf16, on N MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N --steps K --warmup W]            (N=1)
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]            (N=1)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one pass of the hot path (reference train_ac.py:467-504) over one synthetic batch already resident in
@@ -8,7 +8,12 @@ HBM: make_noise -> native UNet forward -> masked MSE -> backward (dX everywhere,
 the flat LoRA gradient bucket] -> global-norm clip + AdamW -> re-pack LoRA operands.  Random-init weights of the
 SD1.5 architecture, synthetic latents [4,4,64,64] and text states [4,77,768] (no datasets/checkpoints offline).
 Gradient checkpointing is OFF (288 GB HBM holds the activations; the reference default ON is a memory workaround).
-Rank 0 prints ONE JSON line.  The `cpu_baseline` leg (N=1 only) times the oracle — checker code, never the product.
+Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else: the box identity and
+fp32-atomics self-check before the run, and after it the roofline kernels, the secondary legs (grad-ckpt on, frozen text
+encoder in the step, the reference-style eager loop) and the `cpu_baseline` leg (N=1 only), which times the oracle —
+checker code, never the product.  --dump-outputs DIR writes what the last timed step left its caller (dump_outputs).
 """
 import argparse
 import json
@@ -28,6 +33,31 @@ FLOP_PER_IMAGE_FULLFT_NOCKPT = 2.41e12    # full fine-tune, ckpt of
 FLOP_PER_IMAGE_CNET_NOCKPT = 2.18e12      # SURVEY §8d without recompute: base fwd 803 + branch fwd 285 + branch bwd 2x285 + decoder dX ~518
 MFMA_BF16_PEAK = 2.5e15                   # MI355X_MICROARCH.md: dense bf16 MFMA
 LORA_PATTERNS = [r"re:.*\.attn.?$", r"re:.*\.ff$"]      # cfgs/train/examples/lora_conventional.yaml:10-12
+DUMP_BUDGET_ELEMS = 16 * 2 ** 20 - 1024   # --dump-outputs: at most 64 MB of float32 in all
+
+
+def dump_outputs(path, loss, tr, moments=True):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy (float32): `loss`, and per trained flat bucket
+    of the trainer (`lora_unet`, `host<i>` = full fine-tune / plugin buckets, `lora_te`) the updated fp32 parameters `<bucket>_params`
+    and — moments=True, NativeTrainer's own optimizer — the AdamW first moment `<bucket>_exp_avg` the step wrote: the fused
+    optimizer kernel clears the gradients, the moment carries them.  An array longer than its share of the 64 MB budget is
+    written as the same fixed, seeded sample of its elements (sorted indices, seed 0) on every run."""
+    import numpy as np
+    states = ([("lora_unet", tr._lora_state)] if tr._lora_state is not None else []) + \
+             [(f"host{i}", st) for i, st in enumerate(tr.host_buckets)] + \
+             ([("lora_te", tr._te_state)] if tr._te_state is not None else [])
+    arrays = [(f"{name}_params", st.bucket.params) for name, st in states]
+    if moments:
+        arrays += [(f"{name}_exp_avg", st.exp_avg) for name, st in states]
+    cap = (DUMP_BUDGET_ELEMS - 1) // max(1, len(arrays))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), np.asarray([float(loss)], dtype=np.float32))
+    for name, t in arrays:
+        t = t.detach().reshape(-1)
+        if t.numel() > cap:
+            idx = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(path, f"{name}.npy"), t.float().cpu().numpy())
 
 
 def _wrap_lora_for_baseline(m, rank):
@@ -64,7 +94,7 @@ def cpu_baseline(batch=4, steps=3, grad_ckpt=True, budget_s=240.0):
     from oracle.unet_sd15 import OracleUNet2DConditionModel, ResnetBlock2D, Transformer2DModel, add_noise, ddpm_alphas_cumprod
     torch.manual_seed(0)
     cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-    cores = max(1, min(cores, 64))
+    cores = max(1, min(cores, int(os.environ.get("OMP_NUM_THREADS") or cores), 64))   # OMP_NUM_THREADS caps it: a CPU quota can be smaller than the affinity mask
     torch.set_num_threads(cores)
     m = OracleUNet2DConditionModel()
     m.requires_grad_(False)
@@ -221,8 +251,11 @@ def main(emu=False):
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--rank-lora", type=int, default=None)
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ckpt-line", action="store_true", help="skip the secondary grad-ckpt-on measurement (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="also the box identity + atomics self-check, the roofline kernels, the secondary legs "
+                    "and the CPU baseline (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the loss and trained buckets of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-ckpt-line", action="store_true", help="with --full: skip the secondary grad-ckpt-on measurement (profiling runs)")
     ap.add_argument("--overlap", action="store_true", help="LoRA wgrad kernels on a side stream (measured slower)")
     ap.add_argument("--no-grouped-wgrad", action="store_true", help="one wgrad launch per layer instead of one grouped launch")
     ap.add_argument("--residual-stream", choices=["auto", "on", "off"], default="auto",
@@ -278,7 +311,7 @@ def main(emu=False):
     if world > 1:
         assert torch.distributed.get_world_size() == args.gpus
 
-    if not emu:
+    if not emu and args.full:
         # which box is this, and do its fp32 atomic adds add?  (one box of round 5 gave wrong sums in every atomics-based
         # kernel for the length of a process; a run on such a box stops here, with the box's identity in the log)
         from hcp_diffusion_amd import kernels as _K
@@ -347,7 +380,7 @@ def main(emu=False):
         torch.manual_seed(114514 + rank)
     else:
         text_encoder = None
-        frozen_te_leg = (args.workload == "sd15" and world == 1 and not emu and not args.no_ckpt_line and not args.no_graph and not args.seam)
+        frozen_te_leg = (args.full and args.workload == "sd15" and world == 1 and not emu and not args.no_ckpt_line and not args.no_graph and not args.seam)
 
         def build_clip():                          # CLIP-L text encoder (cfgs/te_struct.txt), random init
             from hcp_diffusion_amd.text_encoder import NativeCLIPTextModel
@@ -444,6 +477,8 @@ def main(emu=False):
         dt, lv = seam_loop(args.seam_graph, args.steps, args.warmup)
         if not math.isfinite(lv):
             raise RuntimeError(f"bench.py --seam: the training loss after the timed loop is not finite ({lv}): the measurement is void")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, lv, tr, moments=False)      # (the eager loop's optimizer keeps its own moments)
         print(json.dumps({"metric": ("training images/sec, SD1.5 full fine-tune (DreamBooth) 512px bs=%d" % B if fullft else "training images/sec, SD1.5 LoRA 512px bs=4") +
                                     ", native modules driven the reference trainer's way (eager seam)",
                           "value": round(B * args.steps / dt, 2), "unit": "images/sec", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -471,6 +506,8 @@ def main(emu=False):
     loss_ok = math.isfinite(loss_v)
     if not loss_ok:
         print(f"bench.py: the training loss after the timed loop is not finite ({loss_v}): the measurement is void", file=sys.stderr, flush=True)
+    if rank == 0 and args.dump_outputs:            # before any --full leg trains further
+        dump_outputs(args.dump_outputs, loss_v, tr)
     if rank == 0:
         ips = world * B * args.steps / dt
         out = {
@@ -501,12 +538,12 @@ def main(emu=False):
                                                    else FLOP_PER_IMAGE_CNET_NOCKPT if cnet
                                                    else FLOP_PER_IMAGE_LORA_NOCKPT) / MFMA_BF16_PEAK, 4),
         }
-        if not emu:
+        if args.full and not emu:
             # the two roofline kernels are timed HERE, straight after the headline loop: after the grad-ckpt leg below (graphs re-captured,
             # pools released) the caching allocator answers the per-call output allocations with fresh hipMallocs and the 37 us convolution
             # reads 48-60 us (measured, same box, same binary)
             roof, roof_attn = dominant_kernel_roofline(dev), attention_roofline(dev)
-        if world == 1 and args.workload == "sd15" and not args.grad_ckpt and not args.no_graph and not args.no_ckpt_line:
+        if args.full and world == 1 and args.workload == "sd15" and not args.grad_ckpt and not args.no_graph and not args.no_ckpt_line:
             # the reference's default (train_base.yaml:69 gradient_checkpointing: True) timed beside the headline: same
             # trainer, every ResnetBlock2D / Transformer2DModel segment recomputed in backward, graphs re-captured
             unet.enable_gradient_checkpointing()
@@ -565,14 +602,15 @@ def main(emu=False):
                 torch.distributed.barrier()
                 torch.distributed.destroy_process_group()
             return
-        out["roofline"] = roof
-        out["roofline_attention"] = roof_attn
-        if args.workload == "sd15" and B == 4:
-            fam = family_roofline(B)
-            if fam:
-                out["roofline_family"] = fam
-        if world == 1 and not args.no_cpu_baseline and args.workload == "sd15":
-            out["cpu_baseline"] = cpu_baseline()
+        if args.full:
+            out["roofline"] = roof
+            out["roofline_attention"] = roof_attn
+            if args.workload == "sd15" and B == 4:
+                fam = family_roofline(B)
+                if fam:
+                    out["roofline_family"] = fam
+            if world == 1 and not args.no_cpu_baseline and args.workload == "sd15":
+                out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.barrier()

@@ -1,11 +1,14 @@
-"""bench.py's contract with the driver: the launcher guard (one rank per GPU or nothing) on the CPU; on the GPU one short run whose
-single JSON line carries every field the contract names, the roofline record of the dominant kernel and the workload name."""
+"""bench.py's contract with the driver: the launcher guard (one rank per GPU or nothing) and --dump-outputs on the CPU; on the GPU a
+plain run that times the steps only and dumps its outputs, and one --full run whose single JSON line carries every field the contract
+names, the roofline record of the dominant kernel and the workload name."""
 import json
 import os
 import subprocess
 import sys
 from pathlib import Path
+from types import SimpleNamespace
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -77,7 +80,7 @@ def test_abi_comm_bootstrap_falls_back_loudly_when_rccl_cannot_start(monkeypatch
 
 @pytest.mark.gpu
 def test_bench_json_line_contract():
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-ckpt-line"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-ckpt-line"],
                        capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -96,3 +99,73 @@ def test_bench_json_line_contract():
         assert k in rf, k
     assert rf["bound"] == "mfma" and rf["unit"] == "TFLOP/s" and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-3
     assert rf["traffic"] is None or rf["traffic"] > 1e6
+
+
+def _emu_bench(args):
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env.update(OMP_NUM_THREADS="2")
+    r = subprocess.run([sys.executable, str(ROOT / "tests" / "emu" / "bench_emu.py")] + args, env=env, capture_output=True, text=True,
+                       timeout=900, cwd=str(ROOT))
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, (r.stdout[-1500:], r.stderr[-1500:])
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs_same_arguments_same_arrays(tmp_path):
+    """--dump-outputs on the interpreter build: the loss and the trained LoRA bucket of the last timed step as float32 .npy files, the
+    same bits from two runs with the same arguments (seeded inputs), and --steps sets the timed steps."""
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "1", "--rank-lora", "4"]
+    d1 = _emu_bench(args + ["--dump-outputs", str(tmp_path / "a")])
+    d2 = _emu_bench(args + ["--dump-outputs", str(tmp_path / "b")])
+    assert d1["steps"] == 3 and d1["warmup"] == 1 and d1["ms_per_step"] > 0 and "roofline" not in d1 and "cpu_baseline" not in d1
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["lora_unet_exp_avg.npy", "lora_unet_params.npy", "loss.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all()
+        assert np.array_equal(a, b), n
+    assert abs(float(np.load(tmp_path / "a" / "loss.npy")[0]) - d1["final_loss"]) < 1e-5 and d1["final_loss"] == d2["final_loss"]
+    assert np.abs(np.load(tmp_path / "a" / "lora_unet_exp_avg.npy")).max() > 0          # the step's gradients reached the moments
+
+
+def test_dump_outputs_samples_large_buckets_within_the_budget(tmp_path, monkeypatch):
+    """A bucket longer than its share of the budget is written as a fixed seeded sample: the same elements on every call, all of
+    them elements of the bucket, and the files together within the budget."""
+    import torch
+    sys.path.insert(0, str(ROOT))
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_ELEMS", 1001)
+    st = SimpleNamespace(bucket=SimpleNamespace(params=torch.arange(5000, dtype=torch.float32)), exp_avg=-torch.arange(5000, dtype=torch.float32))
+    small = SimpleNamespace(bucket=SimpleNamespace(params=torch.ones(100)), exp_avg=torch.zeros(100))
+    tr = SimpleNamespace(_lora_state=st, host_buckets=[small], _te_state=None)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), 0.5, tr)
+    p = np.load(tmp_path / "a" / "lora_unet_params.npy")
+    assert p.size == 250 and np.all(np.diff(p) >= 0) and np.all(p == np.round(p)) and p.max() < 5000
+    assert np.array_equal(p, np.load(tmp_path / "b" / "lora_unet_params.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "lora_unet_exp_avg.npy"), -p)           # the same indices for every array of a bucket
+    assert np.array_equal(np.load(tmp_path / "a" / "host0_params.npy"), np.ones(100, np.float32))
+    assert sum(np.load(f).size for f in (tmp_path / "a").iterdir()) <= 1001
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
+    """A plain run: the headline line without the --full legs, and the outputs of the last timed step."""
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=900, cwd=str(ROOT))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, "exactly ONE JSON line"
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 2 and d["loss_finite"] is True and d["unit"] == "images/sec" and d["dtype"] == "bf16"
+    for k in ("roofline", "roofline_attention", "roofline_family", "cpu_baseline", "grad_ckpt_on", "frozen_te_in_step", "seam_graph"):
+        assert k not in d, k
+    assert abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) < 0.02 * d["value"]
+    files = {p.name: np.load(p) for p in tmp_path.iterdir()}
+    assert sorted(files) == ["lora_unet_exp_avg.npy", "lora_unet_params.npy", "loss.npy"]
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 * 2 ** 20
+    assert abs(float(files["loss.npy"][0]) - d["final_loss"]) < 1e-5

@@ -9,9 +9,9 @@ cd $root
 python tools/box_info.py > $out/box.json 2>/dev/null      # which box produced this evidence (unique id, partitions, driver, firmware)
 (timeout 1500 python -X faulthandler -m pytest tests -m gpu -v -rP -p no:cacheprovider > $out/gpu_tests.log 2>&1; echo "rc=$?" >> $out/gpu_tests.log)   # verbose + faulthandler: a crash names its test; -rP: the parity lines the full-size tests print
 tail -2 $out/gpu_tests.log
-python bench.py --steps 100 --warmup 20 > $out/bench_sd15.json 2> $out/bench_sd15.err
+python bench.py --full --steps 100 --warmup 20 > $out/bench_sd15.json 2> $out/bench_sd15.err
 for w in sdxl dreambooth controlnet sd15te; do
-  python bench.py --workload $w --no-cpu-baseline > $out/bench_$w.json 2> $out/bench_$w.err
+  python bench.py --full --workload $w --no-cpu-baseline > $out/bench_$w.json 2> $out/bench_$w.err
 done
 python bench.py --seam > $out/bench_seam_sd15.json 2>/dev/null
 python bench.py --seam --seam-graph > $out/bench_seam_graph_sd15.json 2>/dev/null
