@@ -876,6 +876,9 @@ HCP_KERNEL(256) splitk_reduce_kernel(GemmParams p) {
 }
 
 HCP_TUNABLE(int, g_force_cfg, -1);   // tools/tune: force a tile configuration (see hcp_debug_set_gemm_config)
+// g_force_cfg -> (tile id, split-K): values below 1024 are id + 16 * split (ids 0-15), values from 1024 on (id + 64 * split) + 1024 (every id)
+inline int forced_id(int v) { return v >= 1024 ? (v - 1024) % 64 : v % 16; }
+inline int forced_split(int v) { const int s = v >= 1024 ? (v - 1024) / 64 : v / 16; return s > 0 ? s : 1; }
 HCP_TUNABLE(int, g_dbg_ablate, 0);   // tools only, see GemmParams::dbg
 HCP_TUNABLE(int, g_use_glds, 1);     // 1: LDS-DMA main loop (default), 0: register-staged main loop (kept for A/B measurements)
 HCP_TUNABLE(int, g_use_v2, 1);       // 1: buffer-addressed v2 main loop where its requirements hold (default), 0: gemm_glds_kernel everywhere
@@ -962,7 +965,8 @@ int launch_cfg(GemmParams& p, hipStream_t stream) {
 struct TileCfg { int bm, bn; };
 constexpr TileCfg kCfgs[] = {{128, 128}, {128, 64}, {64, 64}, {128, 160}, {64, 160}, {256, 128}, {256, 160}, {128, 320},
                              {128, 160}, {128, 160}, {256, 160},    // 8: 8 waves x 3 stages, 9: 4 waves x 3 stages, 10: 8 waves x 3 stages
-                             {128, 320}, {256, 160}, {128, 160}, {64, 160}, {128, 128}};   // 11: 16 waves (4x4), 12: 16 waves (8x2), 13-15: 8 waves as 4x2
+                             {128, 320}, {256, 160}, {128, 160}, {64, 160}, {128, 128},    // 11: 16 waves (4x4), 12: 16 waves (8x2), 13-15: 8 waves as 4x2
+                             {32, 160}};   // 16: ping-pong kernel only (narrow tile: 256 workgroups at M1024 N1280); elsewhere id 14's kernels
 constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
 
 // p.loaders >= 8: the ping-pong main loop (gemm_pp.hip) with an LDS ring of p.loaders - 8 tiles, where it is instantiated for
@@ -1013,6 +1017,7 @@ int launch_by_id(int id, GemmParams& p, hipStream_t stream) {
         case 13: return launch_cfg<128, 160, 4, 2, MODE, FAST, false, 2, 4>(p, stream);
         case 14: return launch_cfg<64, 160, 4, 2, MODE, FAST, false, 2, 4>(p, stream);
         case 15: return launch_cfg<128, 128, 4, 2, MODE, FAST, false, 2, 4>(p, stream);
+        case 16: return launch_cfg<64, 160, 4, 2, MODE, FAST, false, 2, 4>(p, stream);     // (no ping-pong kernel taken: conv, GEGLU pairing, ring < 8)
         default: return launch_cfg<128, 320, 2, 4, MODE, FAST>(p, stream);
     }
 }
@@ -1032,6 +1037,7 @@ int launch_lora_by_id(int id, GemmParams& p, hipStream_t stream) {
         case 13: return launch_cfg<128, 160, 4, 2, 0, false, true, 2, 4>(p, stream);
         case 14: return launch_cfg<64, 160, 4, 2, 0, false, true, 2, 4>(p, stream);
         case 15: return launch_cfg<128, 128, 4, 2, 0, false, true, 2, 4>(p, stream);
+        case 16: return launch_cfg<64, 160, 4, 2, 0, false, true, 2, 4>(p, stream);        // (no ping-pong kernel taken: GEGLU pairing, ring < 8)
         default: return launch_cfg<64, 160, 2, 2, 0, false, true>(p, stream);
     }
 }
@@ -1089,7 +1095,7 @@ int dispatch_gemm(GemmParams& p, float* ws, size_t ws_bytes, hipStream_t stream)
     int nsplit = 1;
     int id = 0, ld = 0;
     if (!lookup_tuned(p, MODE, &id, &nsplit, &ld)) id = choose_cfg(p, &nsplit);
-    if (g_force_cfg >= 0) { id = g_force_cfg % 16; nsplit = g_force_cfg / 16 > 0 ? g_force_cfg / 16 : 1; }
+    if (g_force_cfg >= 0) { id = forced_id(g_force_cfg); nsplit = forced_split(g_force_cfg); }
     p.loaders = g_force_loaders >= 0 ? g_force_loaders : deepest_ring(ld);
     if (nsplit > 1 && (size_t)nsplit * p.M * p.N * sizeof(float) > ws_bytes) nsplit = 1;
     if (p.geglu_out) nsplit = 1;                             // the pairing epilogue lives in the GEMM kernels, not in the split-K reduce
@@ -1138,7 +1144,7 @@ int launch_lora_dispatched(GemmParams& p, void* workspace, size_t workspace_byte
         else if (p.N % 160 == 0 && (long)p.M * p.N >= (long)4096 * 640) id = 4;
         else id = 2;
     }
-    if (g_force_cfg >= 0) id = g_force_cfg % 16;
+    if (g_force_cfg >= 0) id = forced_id(g_force_cfg);
     p.loaders = g_force_loaders >= 0 ? g_force_loaders : deepest_ring(ld);
     if (id == 7 || id == 10 || id == 11) id = 6;
     if (id < 0) {
@@ -1169,7 +1175,7 @@ HCP_API int hcp_debug_gemm_table_stats(long* hits, long* misses) {
     g_table_hits = 0; g_table_misses = 0;
     return 0;
 }
-// TOOLS ONLY (tools/tune_gemm.py): cfg = tile id + 16 * nsplit; -1 restores the heuristic.
+// TOOLS ONLY (tools/tune_gemm.py): cfg = tile id + 16 * nsplit (ids 0-15), or 1024 + tile id + 64 * nsplit (any id); -1 restores the heuristic.
 HCP_API int hcp_debug_set_gemm_config(int cfg) { g_force_cfg = cfg; return 0; }
 // TOOLS ONLY: 1 = default (v2 main loop where its requirements hold), 0 / 2 = the first LDS-DMA loop (gemm_glds_kernel) everywhere.
 HCP_API int hcp_debug_set_gemm_glds(int on) { g_use_glds = 1; g_use_v2 = on == 1; return 0; }

@@ -41,10 +41,16 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
     constexpr int WTM = BM / 2, WTN = BN / 2;
     constexpr int TM = WTM / 16, TN = WTN / 16;
     constexpr int UPT = 1;                                // units per K tile and group (one k-step each)
-    constexpr int TMF = TM / 2;                           // 16-row blocks a wave finishes (tail + epilogue)
+    // After the exchange a wave finishes half of its tile: half of its 16-row blocks, or — narrow tiles (BM = 32: one row block per
+    // wave) — part of its 16-column blocks: group 0 the first TNF0, group 1 the remaining TNF1 (TN = 5: 3 | 2).  The blocks a wave
+    // finishes sit at register indices 0 .. TNF - 1 (group 1 rotates its accumulators first), so every index stays static.
+    constexpr bool FIN_N = TM == 1;
+    constexpr int TMF = FIN_N ? 1 : TM / 2;               // 16-row blocks a wave finishes (tail + epilogue)
+    constexpr int TNF0 = FIN_N ? (TN + 1) / 2 : TN, TNF1 = FIN_N ? TN / 2 : TN;
+    constexpr int TNF = TNF0;                             // 16-column blocks a wave finishes (group 1 of a narrow tile: TNF1 of them)
     constexpr int RPP = NTL / 8;                          // rows one DMA pass of the loaders covers (32)
     constexpr int A_IT = BM / RPP, B_IT = BN / RPP;
-    static_assert(WTM % 16 == 0 && WTN % 16 == 0 && BM % RPP == 0 && BN % RPP == 0 && TM % 2 == 0, "tile shape");
+    static_assert(WTM % 16 == 0 && WTN % 16 == 0 && BM % RPP == 0 && BN % RPP == 0 && (TM % 2 == 0 || FIN_N), "tile shape");
     static_assert(NST >= 2 && NST <= 4, "ring depth");
     constexpr int A_ELEMS = BM * BK, B_ELEMS = BN * BK, L_ELEMS = LORA ? 32 * BK : 0, BUF_ELEMS = A_ELEMS + B_ELEMS + L_ELEMS;
     constexpr int E_ELEMS = LORA ? BN * 32 : 0;           // E rows of this N tile (loaders, before the ring)
@@ -290,8 +296,10 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
     const int g = wave_all >> 2, gm = (wave_all >> 1) & 1, gn = wave_all & 1;
     const int fr = lane & 15, fg = lane >> 4;
     const int row0 = gm * WTM;                            // first row of this wave's tile in the main loop
-    const int frow0 = gm * WTM + g * (WTM / 2);           // first row of the TMF blocks this wave finishes
+    const int frow0 = FIN_N ? row0 : gm * WTM + g * (WTM / 2);   // first row of the TMF blocks this wave finishes
     const int col0 = gn * WTN;
+    const int fcol0 = col0 + (FIN_N ? g * TNF0 * 16 : 0);  // first column of the TNF blocks this wave finishes
+    const int nfin = FIN_N && g == 1 ? TNF1 : TNF0;       // ... of which this many are its own (wave-uniform)
     // fragment addresses (elements) inside a ring slot: row R, 16-byte slot (ks*4 + fg) ^ ((R >> 1) & 7); the swizzle term only
     // depends on fr because every 16-row block starts at a multiple of 16; k-step 1 = k-step 0 XOR 32 elements
     const int sw0 = ((fg ^ ((fr >> 1) & 7)) << 3) ^ (g * 32);
@@ -314,12 +322,12 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
     // per-element s_waitcnt) in front of the stores.
     constexpr bool EARLY = !(LORA && TM * TN >= 20);      // request them BEFORE the loop wherever the registers exist: a late request
                                                           // leaves ~2 us of round trip exposed (measured: conv C320 64x64 36.3 -> 38.2 us)
-    hcp_f32x4 bias_v[TN];
-    hcp_bf16x4 res_v[TMF][TN];
+    hcp_f32x4 bias_v[TNF];
+    hcp_bf16x4 res_v[TMF][TNF];
     auto load_bias = [&]() {                              // 640 bytes shared by every workgroup of the N tile: an L2 hit, requested late
         const hcp_rsrc rbias = hcp_make_rsrc_n(p.bias, p.bias ? (unsigned)p.N * 4u : 0u);
 #pragma unroll
-        for (int j = 0; j < TN; ++j) bias_v[j] = hcp_buf_load16f(rbias, (unsigned)geglu_col(p, BN, n0 + col0 + j * 16 + 4 * fg) * 4u);
+        for (int j = 0; j < TNF; ++j) bias_v[j] = hcp_buf_load16f(rbias, (unsigned)geglu_col(p, BN, n0 + fcol0 + j * 16 + 4 * fg) * 4u);
     };
     // Rows past M need no select: their offset is >= the resource's num_records (ldr >= N), so the hardware range check returns zeros —
     // and a `m < M ? offset : OOB` select here compiled to divergent branches with a WAW `s_waitcnt vmcnt(0)` between the loads: TMF
@@ -330,8 +338,8 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
         for (int i = 0; i < TMF; ++i) {
             const int m = m0 + frow0 + i * 16 + fr;
 #pragma unroll
-            for (int j = 0; j < TN; ++j)
-                res_v[i][j] = hcp_buf_load8(rres, ((unsigned)m * (unsigned)p.ldr + (unsigned)(n0 + col0 + j * 16 + 4 * fg)) * 2u);
+            for (int j = 0; j < TNF; ++j)
+                res_v[i][j] = hcp_buf_load8(rres, ((unsigned)m * (unsigned)p.ldr + (unsigned)(n0 + fcol0 + j * 16 + 4 * fg)) * 2u);
         }
     };
 
@@ -385,17 +393,47 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
     // ---- the two groups' partial sums meet: a wave stores the row blocks its partner will finish and adds the partner's partial
     // of its own; [wave][block][column block][lane] in 16-byte pieces = conflict-free, 16 KB per (wave, block row).  Group 1
     // first swaps its halves so that both groups keep blocks 0 .. TMF-1 of the arrays (static register indices).
-    if (g == 1) {
+    // Narrow tiles: the partners hold partials of the same 16 x WTN block.  Group 1 rotates its column blocks left by TNF0 (its own
+    // TNF1 come first); a wave hands over the column blocks its partner finishes ([wave][slot][lane], TNF0 slots), group 1 also its
+    // T partial (group 0 finishes T: the LoRA tail's T image is written once).
+    hcp_f32x4* const xb = (hcp_f32x4*)ring;
+    hcp_f32x4* const xt = xb + NC * TMF * (FIN_N ? TNF0 : TN) * 64;
+    const int pw = wave_all ^ 4;
+    if constexpr (FIN_N) {
+        if (g == 1) {
+            hcp_f32x4 tmp[TN];
 #pragma unroll
-        for (int i = 0; i < TMF; ++i) {
+            for (int j = 0; j < TN; ++j) tmp[j] = acc[0][j];
 #pragma unroll
-            for (int j = 0; j < TN; ++j) { const hcp_f32x4 tmp = acc[i][j]; acc[i][j] = acc[TMF + i][j]; acc[TMF + i][j] = tmp; }
-            if (LORA) { const hcp_f32x4 tmp = tacc[i]; tacc[i] = tacc[TMF + i]; tacc[TMF + i] = tmp; }
+            for (int j = 0; j < TN; ++j) acc[0][j] = tmp[(j + TNF0) % TN];
         }
-    }
-    {
-        hcp_f32x4* const xb = (hcp_f32x4*)ring;
-        hcp_f32x4* const xt = xb + NC * TMF * TN * 64;
+        if (g == 0) {
+#pragma unroll
+            for (int k = 0; k < TNF1; ++k) xb[(wave_all * TNF0 + k) * 64 + lane] = acc[0][TNF0 + k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < TNF0; ++k) xb[(wave_all * TNF0 + k) * 64 + lane] = acc[0][TNF1 + k];
+            if (LORA) xt[wave_all * 64 + lane] = tacc[0];
+        }
+        if (p.nsplit == 1) load_bias();                   // the round trip hides under the exchange
+        hcp_barrier_keep_dma();
+        if (g == 0) {
+#pragma unroll
+            for (int k = 0; k < TNF0; ++k) acc[0][k] += xb[(pw * TNF0 + k) * 64 + lane];
+            if (LORA) tacc[0] += xt[pw * 64 + lane];
+        } else {
+#pragma unroll
+            for (int k = 0; k < TNF1; ++k) acc[0][k] += xb[(pw * TNF0 + k) * 64 + lane];
+        }
+    } else {
+        if (g == 1) {
+#pragma unroll
+            for (int i = 0; i < TMF; ++i) {
+#pragma unroll
+                for (int j = 0; j < TN; ++j) { const hcp_f32x4 tmp = acc[i][j]; acc[i][j] = acc[TMF + i][j]; acc[TMF + i][j] = tmp; }
+                if (LORA) { const hcp_f32x4 tmp = tacc[i]; tacc[i] = tacc[TMF + i]; tacc[TMF + i] = tmp; }
+            }
+        }
 #pragma unroll
         for (int i = 0; i < TMF; ++i) {
 #pragma unroll
@@ -404,15 +442,14 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
         }
         if (p.nsplit == 1) load_bias();                   // the round trip hides under the exchange
         hcp_barrier_keep_dma();
-        const int pw = wave_all ^ 4;
 #pragma unroll
         for (int i = 0; i < TMF; ++i) {
 #pragma unroll
             for (int j = 0; j < TN; ++j) acc[i][j] += xb[((pw * TMF + i) * TN + j) * 64 + lane];
             if (LORA) tacc[i] += xt[(pw * TMF + i) * 64 + lane];
         }
-        hcp_barrier_keep_dma();                           // the exchange area is the ring: the LoRA tail re-uses it
     }
+    hcp_barrier_keep_dma();                               // the exchange area is the ring: the LoRA tail re-uses it
 
     if (LORA) {
         // T (bf16-rounded) and E = alpha * W_up rows of this N tile meet in LDS; one extra k-step adds T E^T
@@ -423,6 +460,7 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
         const int ldt = split ? 64 : 32;
 #pragma unroll
         for (int i = 0; i < TMF; ++i) {
+            if (FIN_N && g == 1) break;                     // (narrow tile: group 0 holds the summed T block)
             hcp_bf16x4 o, o2;
             lora_t_split(tacc[i], o, o2);
             const int ml = frow0 + i * 16 + fr;
@@ -435,22 +473,23 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
         }
         if (!EARLY && p.nsplit == 1 && !p.epi_tile) load_residual();
         HCP_SYNC();
-        hcp_bf16x8 ft[TMF], fe[TN];
+        hcp_bf16x8 ft[TMF], fe[TNF];
 #pragma unroll
         for (int i = 0; i < TMF; ++i) ft[i] = *(const hcp_bf16x8*)(lt + (frow0 + i * 16 + fr) * TS2 + fg * 8);
 #pragma unroll
-        for (int j = 0; j < TN; ++j) fe[j] = *(const hcp_bf16x8*)(lds_e + (col0 + j * 16 + fr) * 32 + fg * 8);
+        for (int j = 0; j < TNF; ++j) fe[j] = *(const hcp_bf16x8*)(lds_e + (fcol0 + j * 16 + fr) * 32 + fg * 8);
+        // (group 1 of a narrow tile: slot TNF - 1 is not its own — it reads past the E image, inside the ring, and is never stored)
 #pragma unroll
         for (int i = 0; i < TMF; ++i)
 #pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = hcp_mfma16(fe[j], ft[i], acc[i][j]);
+            for (int j = 0; j < TNF; ++j) acc[i][j] = hcp_mfma16(fe[j], ft[i], acc[i][j]);
         if (split) {
 #pragma unroll
             for (int i = 0; i < TMF; ++i) ft[i] = *(const hcp_bf16x8*)(lt2 + (frow0 + i * 16 + fr) * TS2 + fg * 8);
 #pragma unroll
             for (int i = 0; i < TMF; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = hcp_mfma16(fe[j], ft[i], acc[i][j]);
+                for (int j = 0; j < TNF; ++j) acc[i][j] = hcp_mfma16(fe[j], ft[i], acc[i][j]);
         }
     }
 
@@ -460,9 +499,9 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
             const int m = m0 + frow0 + i * 16 + fr;
             if (m >= p.M) continue;
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int n = n0 + col0 + j * 16 + 4 * fg;
-                if (n < p.N) *(hcp_f32x4*)(p.slabs + ((size_t)split * p.M + m) * p.N + n) = acc[i][j];
+            for (int j = 0; j < TNF; ++j) {
+                const int n = n0 + fcol0 + j * 16 + 4 * fg;
+                if (j < nfin && n < p.N) *(hcp_f32x4*)(p.slabs + ((size_t)split * p.M + m) * p.N + n) = acc[i][j];
             }
         }
         return;
@@ -472,12 +511,13 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
 #pragma unroll
         for (int i = 0; i < TMF; ++i)
 #pragma unroll
-            for (int j = 0; j < TN; ++j) geglu_tile_put(ring, geglu_tile_ld(BN), frow0 + i * 16 + fr, col0 + j * 16 + 4 * fg, acc[i][j], p.alpha);
+            for (int j = 0; j < TNF; ++j)
+                if (j < nfin) geglu_tile_put(ring, geglu_tile_ld(BN), frow0 + i * 16 + fr, fcol0 + j * 16 + 4 * fg, acc[i][j], p.alpha);
         HCP_SYNC();
         geglu_tile_apply<BM, BN, NTC>(p, ring, m0, n0, tid_all);
         return;
     }
-    if (p.geglu_out) {                                      // GEGLU-forward epilogue (gemm_params.h: geglu_out): D = bf16(h | g), geglu_out = bf16(h gelu(g))
+    if constexpr (!FIN_N) if (p.geglu_out) {                // GEGLU-forward epilogue (gemm_params.h: geglu_out): D = bf16(h | g), geglu_out = bf16(h gelu(g))
         static_assert((size_t)BM * BN * 2 <= (size_t)NST * BUF_ELEMS * sizeof(hcp_bf16), "the gelu(g) tile fits the ring");
         if (LORA) HCP_SYNC();                               // the LoRA tail's T image lives in the ring
         hcp_f32x4 v[TMF][TN];
@@ -506,8 +546,9 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
             const int ml = frow0 + i * 16 + fr, m = m0 + ml;
             const float* rbp = (p.rowbias && m < p.M) ? p.rowbias + (size_t)(m / p.rows_per_group) * p.rowbias_ld : nullptr;
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int nl = col0 + j * 16 + 4 * fg;
+            for (int j = 0; j < TNF; ++j) {
+                if (j >= nfin) continue;
+                const int nl = fcol0 + j * 16 + 4 * fg;
                 hcp_f32x4 v = acc[i][j] * p.alpha + bias_v[j];
                 if (rbp && n0 + nl < p.N) v += *(const hcp_f32x4*)(rbp + n0 + nl);
                 *(hcp_f32x4*)(tile + ml * epi_tile_ld(BN) + nl) = v;
@@ -521,20 +562,20 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
     for (int i = 0; i < TMF; ++i) {
         const int m = m0 + frow0 + i * 16 + fr;
         if (m >= p.M) continue;
-        hcp_f32x4 rb_v[TN];
+        hcp_f32x4 rb_v[TNF];
         if (p.rowbias) {
             const float* rbp = p.rowbias + (size_t)(m / p.rows_per_group) * p.rowbias_ld;
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int n = n0 + col0 + j * 16 + 4 * fg;
+            for (int j = 0; j < TNF; ++j) {
+                const int n = n0 + fcol0 + j * 16 + 4 * fg;
                 hcp_f32x4 z = {0.f, 0.f, 0.f, 0.f};
                 rb_v[j] = n < p.N ? *(const hcp_f32x4*)(rbp + n) : z;
             }
         }
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = n0 + col0 + j * 16 + 4 * fg;
-            if (n >= p.N) continue;
+        for (int j = 0; j < TNF; ++j) {
+            const int n = n0 + fcol0 + j * 16 + 4 * fg;
+            if (j >= nfin || n >= p.N) continue;
             hcp_f32x4 v = acc[i][j] * p.alpha + bias_v[j];
             if (p.rowbias) v += rb_v[j];
             if (p.residual) {
@@ -552,8 +593,9 @@ template <int BM, int BN, int MODE, bool LORA>
 int launch_pp(GemmParams& p, int ring, hipStream_t stream) {
     constexpr size_t stage = (size_t)(BM + BN + (LORA ? 32 : 0)) * BK * sizeof(hcp_bf16);
     constexpr size_t eimg = LORA ? (size_t)BN * 32 * sizeof(hcp_bf16) : 0;
-    constexpr int TMF = BM / 64;
-    constexpr size_t xchg = (size_t)8 * TMF * (BN / 32) * 64 * 16 + (LORA ? (size_t)8 * TMF * 64 * 16 : 0);   // the groups' exchange area
+    constexpr int TM = BM / 32, TN = BN / 32;
+    constexpr int TMF = TM == 1 ? 1 : TM / 2, TNX = TM == 1 ? (TN + 1) / 2 : TN;      // (the kernel's TMF and exchange slots per block row)
+    constexpr size_t xchg = (size_t)8 * TMF * TNX * 64 * 16 + (LORA ? (size_t)8 * TMF * 64 * 16 : 0);   // the groups' exchange area
     constexpr size_t tail = LORA ? (size_t)2 * BM * 40 * sizeof(hcp_bf16) : 0;   // T_hi and T_lo images
     constexpr size_t tile_bytes = (size_t)BM * epi_tile_ld(BN) * sizeof(float);     // tile epilogue (lives in the ring like the exchange area)
     if (p.epi_tile && tile_bytes + eimg > 160 * 1024) p.epi_tile = 0;
@@ -589,6 +631,10 @@ int gemm_pp_launch(GemmParams& p, int bm, int bn, int mode, bool lora, int ring,
     if (p.residual && (size_t)p.M * p.ldr * 2 >= (1ul << 31)) return -2;       // 32-bit buffer offsets
     if (bm == 128 && bn == 160) return launch_pp_mode<128, 160>(p, mode, lora, ring, stream);
     if (bm == 64 && bn == 160) return launch_pp_mode<64, 160>(p, mode, lora, ring, stream);
+    if (bm == 32 && bn == 160) {                                               // narrow tile: plain / fused-LoRA GEMMs, no GEGLU pairing
+        if (mode != 0 || p.geglu_out) return -2;
+        return lora ? launch_pp<32, 160, 0, true>(p, ring, stream) : launch_pp<32, 160, 0, false>(p, ring, stream);
+    }
     if (bm == 128 && bn == 128) return launch_pp_mode<128, 128>(p, mode, lora, ring, stream);
     return -2;
 }

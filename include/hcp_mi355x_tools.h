@@ -8,7 +8,7 @@
 extern "C" {
 #endif
 int hcp_debug_gemm_table_stats(long* hits, long* misses); /* tools only: dispatch-table lookups since the last call; resets */
-int hcp_debug_set_gemm_config(int cfg); /* tools/tune_gemm.py only: force tile id + 16*nsplit, -1 = heuristic */
+int hcp_debug_set_gemm_config(int cfg); /* tools/tune_gemm.py only: force tile id + 16*nsplit (ids 0-15) or 1024 + id + 64*nsplit (any id), -1 = heuristic */
 int hcp_debug_set_gemm_ablation(int flags); /* tools only (wrong results when != 0): 1 no DMA, 2 no MFMA, 4 no LDS reads */
 int hcp_debug_set_gn_target(int workgroups);   /* tools only: workgroups a two-launch GroupNorm aims for (default 512); -1 / -2: one-launch slab path off / on */
 int hcp_debug_set_gemm_epilogue(int mode); /* tools only: -1 size rule, 0 lane-layout epilogue, 1 tile epilogue (16-byte row pieces through LDS) where possible */
