@@ -79,6 +79,11 @@ _PROTOTYPES = {
     "hcp_snr_loss_weight": (I, [P, P, P, I, I, F, P]),
     "hcp_quick_gelu": (I, [P, P, P, L, P]),
     "hcp_embedding_bf16": (I, [P, P, P, P, P, L, I, I, P]),
+    # ids, B, R, W, n_word, token_table, vocab, position_table, position_ids, n_pos, custom_table, n_custom, custom_map, n_map, out,
+    # src_map, C, stream
+    "hcp_embedding_pt_fwd_bf16": (I, [P, I, I, I, I, P, I, P, P, I, P, I, P, I, P, P, I, P]),
+    # dX, src_map, M, C, grad, n_custom, beta, stream
+    "hcp_embedding_pt_bwd_f32": (I, [P, P, L, I, P, I, I, P]),
     "hcp_transpose_bf16": (I, [P, P, I, I, I, P]),
     "hcp_softmax_rows": (I, [P, L, P, L, I, I, F, P]),
     "hcp_vae_latent_sample": (I, [P, P, P, P, P, I, I, L, F, P]),
@@ -127,7 +132,7 @@ TOOLS_SYMBOLS = tuple(_TOOLS_PROTOTYPES)
 TOOLS_LIB_PATH = Path(__file__).resolve().parent / "libhcp_mi355x_tools.so"
 
 
-ABI_VERSION = 3          # include/hcp_mi355x.h HCP_ABI_VERSION: bumped whenever an exported signature or descriptor layout changes
+ABI_VERSION = 4          # include/hcp_mi355x.h HCP_ABI_VERSION: bumped whenever an exported signature or descriptor layout changes
 
 
 class HcpError(RuntimeError):

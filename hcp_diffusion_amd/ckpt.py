@@ -80,6 +80,24 @@ class _EMAView:
         return self._sd
 
 
+def save_emb(path, emb, replace=False):
+    """utils/net_utils.py:154-160: ``{'string_to_param': {'*': emb}, 'name': name}`` (a host copy of just the vectors: a view into a
+    trainer's flat bucket would otherwise pickle the whole bucket)."""
+    name = os.path.basename(path)
+    if os.path.exists(path) and not replace:
+        raise FileExistsError(f'embedding "{name}" already exist.')
+    torch.save({"string_to_param": {"*": emb.detach().to("cpu").clone()}, "name": name[:name.rfind(".")]}, path)
+    return path
+
+
+def load_emb(path):
+    """utils/net_utils.py:145-152: the vectors of a word file, either layout (``string_to_param`` or ``emb_params``)."""
+    state = torch.load(path, map_location="cpu")
+    emb = state["string_to_param"]["*"] if "string_to_param" in state else state["emb_params"]
+    emb.requires_grad_(False)
+    return emb
+
+
 class CkptManagerNative:
     """Method surface of CkptManagerPKL / CkptManagerSafe for the UNet half (ckpt_pkl.py:22-79); ``fmt`` picks the
     container: 'safetensors' (CkptManagerSafe) or 'ckpt' (CkptManagerPKL)."""
@@ -119,6 +137,16 @@ class CkptManagerNative:
             if model_ema is not None:
                 sd["plugin_ema"] = group.state_dict(model_ema)
             paths.append(self._save_ckpt(sd, f"{name}-{plugin_name}", step))
+        return paths
+
+    def save_embedding(self, train_pts, step, replace):
+        """CkptManagerPKL.save_embedding (ckpt_pkl.py:98-103): ``{word}-{step}.pt`` per trained word, and ``{word}.pt`` in the
+        embedding directory when ``replace``."""
+        paths = []
+        for k, v in train_pts.items():
+            paths.append(save_emb(os.path.join(self.save_dir, f"{k}-{step}.pt"), v.data, replace=True))
+            if replace:
+                paths.append(save_emb(os.path.join(self.emb_dir or "", f"{k}.pt"), v.data, replace=True))
         return paths
 
     def _save_ckpt(self, sd_model, name=None, step=None, save_path=None):

@@ -770,3 +770,38 @@ def ema_update(ema, p, step, inv_gamma=1.0, power=2.0 / 3.0, decay_max=0.9997):
     assert step.dtype == torch.int32
     _chk(lib().hcp_ema_update(_p(ema), _p(p), p.numel(), _p(step), float(inv_gamma), float(power), float(decay_max), _stream(p)),
          "hcp_ema_update")
+
+
+def embedding_pt_fwd(token_table, ids, position_table, n_repeats, n_word, position_ids=None, custom_table=None, custom_map=None):
+    """Prompt tuning (EmbeddingPTHook + CLIPTextEmbeddings): ids int64 [B, r*w] -> (bf16 [B*r, n_word+2, C], int32 source map
+    [B*r, n_word+2]).  custom_table fp32 [n_custom, C], custom_map int32 [n_map, 2] = (row offset, n_vec) of token id vocab + i;
+    position_ids int64 [B*r, n_word+2] or None (arange)."""
+    assert token_table.dtype == torch.float32 and position_table.dtype == torch.float32 and token_table.is_contiguous() and position_table.is_contiguous()
+    assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.is_contiguous() and ids.shape[1] % n_repeats == 0
+    B, R = ids.shape[0], int(n_repeats)
+    W, WO, C = ids.shape[1] // R, n_word + 2, token_table.shape[1]
+    if position_ids is not None:
+        assert position_ids.dtype == torch.int64 and position_ids.is_contiguous() and position_ids.numel() == B * R * WO
+    n_custom = n_map = 0
+    if custom_map is not None and custom_map.numel():
+        assert custom_map.dtype == torch.int32 and custom_map.is_contiguous() and custom_map.shape[-1] == 2
+        assert custom_table is not None and custom_table.dtype == torch.float32 and custom_table.is_contiguous() and custom_table.shape[1] == C
+        n_custom, n_map = custom_table.shape[0], custom_map.shape[0]
+    out = torch.empty((B * R, WO, C), dtype=BF16, device=ids.device)
+    src = torch.empty((B * R, WO), dtype=torch.int32, device=ids.device)
+    _chk(lib().hcp_embedding_pt_fwd_bf16(_p(ids), B, R, W, n_word, _p(token_table), token_table.shape[0], _p(position_table), _p(position_ids),
+                                         position_table.shape[0], _p(custom_table) if n_map else None, n_custom,
+                                         _p(custom_map) if n_map else None, n_map, _p(out), _p(src), C, _stream(ids)),
+         "hcp_embedding_pt_fwd_bf16")
+    return out, src
+
+
+def embedding_pt_bwd(dx, src_map, grad, accumulate=False):
+    """grad fp32 [n_custom, C] (accumulate: +)= per custom row, the sum of dx (bf16 [.., C]) over the rows src_map sends to it."""
+    assert dx.dtype == BF16 and dx.is_contiguous() and src_map.dtype == torch.int32 and src_map.is_contiguous()
+    assert grad.dtype == torch.float32 and grad.is_contiguous() and grad.dim() == 2 and grad.shape[1] == dx.shape[-1]
+    M = src_map.numel()
+    assert dx.numel() == M * grad.shape[1]
+    _chk(lib().hcp_embedding_pt_bwd_f32(_p(dx), _p(src_map), M, grad.shape[1], _p(grad), grad.shape[0], int(bool(accumulate)), _stream(dx)),
+         "hcp_embedding_pt_bwd_f32")
+    return grad

@@ -942,3 +942,44 @@ def conv_in(sample, host):
     if hw is None and hb is None:
         return K.conv3x3(x, pk.w, pk.cout, bias=pk.bias)
     return _ConvInFn.apply(x, host, hw, hb)
+
+
+class _EmbeddingPTFn(torch.autograd.Function):
+    """Prompt tuning (EmbeddingPTHook.forward + CLIPTextEmbeddings, text_emb_ex.py:38-69): ids [B, r*w] -> bf16 [B*r, N_word+2, C].
+    The inputs autograd sees are the custom words' vectors; the token and position tables stay frozen.  Backward: every vector's
+    gradient is the sum of dX over the output rows it landed in (hcp_embedding_pt_bwd_f32).  With a flat gradient sink on the hook
+    (prompt_tuning.PTBucket: NativeTrainer) the kernel adds into it and autograd gets no per-parameter gradient."""
+
+    @staticmethod
+    def forward(ctx, ids, position_ids, tok, pos, hook, lay, *params):
+        out, src = K.embedding_pt_fwd(tok, ids, pos, hook.N_repeats, hook.N_word, position_ids=position_ids, custom_table=lay.table(),
+                                      custom_map=lay.cmap if lay.params else None)
+        ctx.save_for_backward(src)
+        ctx.hook, ctx.lay = hook, lay
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        src, = ctx.saved_tensors
+        lay, none = ctx.lay, (None,) * 6
+        need = ctx.needs_input_grad[6:]
+        dy = dy.to(BF16).contiguous()
+        sink = getattr(ctx.hook, "_pt_sink", None)
+        if sink is not None:                            # trained words first in the table: their rows are the sink's rows
+            K.embedding_pt_bwd(dy, src, sink, accumulate=True)
+            return none + (None,) * len(lay.params)
+        if not any(need):
+            return none + (None,) * len(lay.params)
+        g = K.embedding_pt_bwd(dy, src, torch.empty((lay.n_rows, dy.shape[-1]), dtype=torch.float32, device=dy.device))
+        grads, off = [], 0
+        for p, n, want in zip(lay.params, lay.rows, need):
+            grads.append(g[off:off + n].view(p.shape).to(p.dtype) if want else None)
+            off += n
+        return none + tuple(grads)
+
+
+def embedding_pt(ids, tok, pos, hook, position_ids=None):
+    """Token + position embedding with the custom words of an ``emb_ex`` hook (prompt_tuning.py)."""
+    from .prompt_tuning import layout
+    lay = layout(hook, ids.device)
+    return _EmbeddingPTFn.apply(ids, position_ids, tok, pos, hook, lay, *lay.params)

@@ -9,7 +9,8 @@ Same module tree, parameter names and shapes as transformers' ``CLIPTextModel`` 
 (``text_model.embeddings.token_embedding`` ... ``text_model.final_layer_norm``), so checkpoints load by name and the
 ``re:.*self_attn$`` / ``re:.*mlp$`` selectors wrap the same Linear leaves.  Every leaf is a ``HipLinear`` / ``HipLayerNorm``:
 LoRA blocks are the UNet's own ``LoraHipLayer`` (one flat bucket, grouped weight-gradient launch, fused clip + AdamW).
-Kernels: ``hcp_embedding_bf16``, LayerNorm, fused-LoRA GEMM, flash attention with ``causal=1`` (12 x 64 heads, 77 tokens),
+Kernels: ``hcp_embedding_bf16`` (or, with a prompt-tuning ``emb_ex`` hook on ``token_embedding``,
+``hcp_embedding_pt_fwd_bf16`` / ``_bwd_f32``: prompt_tuning.py), LayerNorm, fused-LoRA GEMM, flash attention with ``causal=1`` (12 x 64 heads, 77 tokens),
 ``hcp_quick_gelu``.  Output selection follows ``TEEXHook.forward_hook`` (textencoder_ex.py:62-79) for N_repeats = 1:
 ``final_layer_norm(hidden_states[-clip_skip-1])``; ``N_repeats`` > 1 (``tokenizer_repeats``) encodes [B, r x 77] ids as B r prompts and stitches
 the chunks back with one BOS and one EOS, as the hook does.
@@ -111,6 +112,9 @@ class NativeCLIPTextModel(nn.Module):
     def dtype(self):                                   # utils/pipe_hook.py:25-26 casts the prompt states to text_encoder.dtype
         return self.text_model.final_layer_norm.weight.dtype
 
+    def get_input_embeddings(self):              # transformers' CLIPTextModel API: EmbeddingPTHook.hook attaches its plugin here
+        return self.text_model.embeddings.token_embedding
+
     def enable_hip_graph(self, on=True):
         """As NativeUNet2DConditionModel.enable_hip_graph: under an ordinary eager trainer loop the encoder's forward and backward
         (text-encoder LoRA training, lora_conventional.yaml:14-19) replay captured hipGraphs, one pair per input signature."""
@@ -121,7 +125,11 @@ class NativeCLIPTextModel(nn.Module):
         if (getattr(self, "_hip_graph", False) and torch.is_grad_enabled() and input_ids.is_cuda
                 and not torch.cuda.is_current_stream_capturing()):
             from . import graphed
-            if graphed.capturable_cached(self)[0]:
+            # prompt tuning stays eager: the hook's word dict is Python state read at every call (words can be added or re-homed between
+            # steps, like the per-step forward hooks capturable() refuses), and the custom vectors' gradient leaves through autograd or
+            # the trainer's sink, not through the LoRA / host buckets the captured backward writes.  (NativeTrainer(use_graph=True)
+            # captures the whole step, the prompt-tuning kernels included.)
+            if getattr(self.text_model.embeddings.token_embedding, "emb_ex", None) is None and graphed.capturable_cached(self)[0]:
                 ins = [input_ids, position_ids, attention_mask]
                 key = tuple(None if t is None else (tuple(t.shape), t.dtype) for t in ins)
                 x = graphed.call(self, ins, lambda i_, p_, m_: self._forward_impl(i_, p_, m_), self._hip_graphs, key)
@@ -136,6 +144,7 @@ class NativeCLIPTextModel(nn.Module):
         (pooled_output None: CLIP-L's pooled vector is not used by the SD1.x path)."""
         tm = self.text_model
         B, r = input_ids.shape[0], self.N_repeats
+        ids_in = input_ids
         if r > 1:                                                 # TEEXHook.forward_hook_input (textencoder_ex.py:57-59): 'b (r w) -> (b r) w'
             if input_ids.dim() != 2 or input_ids.shape[1] % r:
                 raise ValueError(f"token ids [B, {r} x L] expected for N_repeats={r}, got {tuple(input_ids.shape)}")
@@ -148,8 +157,19 @@ class NativeCLIPTextModel(nn.Module):
             raise ValueError(f"attention_mask {tuple(attention_mask.shape)} does not match input_ids {tuple(input_ids.shape)}")
         emb = tm.embeddings
         if torch.is_grad_enabled() and (emb.token_embedding.weight.requires_grad or emb.position_embedding.weight.requires_grad):
-            raise NotImplementedError("hcp_diffusion_amd: training the embedding tables (prompt tuning) is not implemented")
-        x = K.embedding(emb.token_embedding.weight.detach(), input_ids.contiguous(), emb.position_embedding.weight.detach(), position_ids)
+            raise NotImplementedError("hcp_diffusion_amd: the token / position tables are frozen (prompt tuning trains custom words: prompt_tuning.py)")
+        hook = getattr(emb.token_embedding, "emb_ex", None)
+        if hook is None:
+            x = K.embedding(emb.token_embedding.weight.detach(), input_ids.contiguous(), emb.position_embedding.weight.detach(), position_ids)
+        else:                   # prompt tuning: EmbeddingPTHook's pre-hook regroups the ids to [B, r*w] (text_emb_ex.py:33-36)
+            from .prompt_tuning import check_ids
+            if hook.N_repeats != r or input_ids.shape[1] != hook.N_word + 2:
+                raise ValueError(f"prompt tuning: the embedding hook expects N_repeats={hook.N_repeats} chunks of {hook.N_word + 2} ids, "
+                                 f"the encoder has N_repeats={r} and {input_ids.shape[1]} ids per chunk")
+            ids_b = ids_in.reshape(B, -1).contiguous()
+            check_ids(hook, ids_b)
+            x = ops.embedding_pt(ids_b, emb.token_embedding.weight.detach(), emb.position_embedding.weight.detach(), hook,
+                                 position_ids.contiguous() if position_ids is not None else None)
         key_bias = None
         if attention_mask is not None:       # [B, L], 1 = attend (wrapper.py:20 passes the tokenizer's mask when encoder_attention_mask is on)
             key_bias = ((1.0 - attention_mask.to(torch.float32)) * -1.0e9).contiguous()       # additive on the keys, on top of the causal mask

@@ -129,7 +129,7 @@ class NativeTrainer:
                  scale_lr_factor=1.0, process_group=None, use_graph=False, loss_weight=1.0, num_train_timesteps=1000,
                  overlap_wgrad=False, grouped_wgrad=True, train_cfg=None, plugins=None, ema=None, loss_cfg=None, text_encoder=None,
                  lora_te_cfg=None, comm=None, shard_optimizer=None, gradient_accumulation_steps=1, loss_type="eps",
-                 overlap_exchange=False, grad_wire="fp32", param_wire="fp32"):
+                 overlap_exchange=False, grad_wire="fp32", param_wire="fp32", pt_cfg=None, pt_words=None, pt_weight_decay=5e-4):
         """lora_cfg: the reference's ``lora_unet`` list ({layers, rank, alpha, lr, ...}); train_cfg: its ``unet`` list
         ({layers, lr}) of host modules to fine-tune in full (DreamBooth.yaml:6-10 uses ``layers: ['']`` = everything);
         plugins: [(plugin module, lr)] — trainable hook plugins such as controlnet.ControlNetHipPlugin (make_plugin,
@@ -153,7 +153,13 @@ class NativeTrainer:
         backward has passed it, under the rest of backward (torch DDP overlaps its buckets the same way: reducer hooks, train_ac.py:117);
         grad_wire='bf16': gradients are rounded to bf16 for the reduce-scatter (DDP's bf16_compress_hook numerics); param_wire='bf16':
         the all-gather returns the updated parameters as bf16 — bit-identical bf16 operands on every rank, but the fp32 masters of a
-        slice are then current on its owner only (`sync_masters()`, a collective, re-gathers them; save_model insists on it)."""
+        slice are then current on its owner only (`sync_masters()`, a collective, re-gathers them; save_model insists on it).
+        Prompt tuning — pt_cfg: the reference's ``tokenizer_pt.train`` list ([{name, lr}]), pt_words: {name: Parameter} (its
+        ``ex_words_emb``, every word registered in the ``emb_ex`` hook on ``text_encoder``): the trained words form one flat fp32 bucket
+        with one lr segment per word (``scale_lr_pt``: the same scale_lr_factor), stepped by the fused AdamW with pt_weight_decay
+        (train_base.yaml:42-55 ``optimizer_pt``).  They join the global-norm clip only when the text encoder trains too
+        (TE_unet.trainable_parameters() then holds the hook's emb_train, train_ac.py:483-490); the exchange and the captured step
+        cover them like every bucket."""
         self.unet = unet
         self.device = next(unet.parameters()).device
         self.comm = comm if comm is not None else make_comm(self.device, process_group)
@@ -193,7 +199,7 @@ class NativeTrainer:
             self.host_buckets.append(_OptState(hb, plr * scale_lr_factor, self.device, comm=self.comm, shard=shard, **wires))
             self.plugins.append(plugin)
         self.param_groups, self.lora_group, self.bucket = make_lora(unet, lora_cfg) if lora_cfg else ([], None, None)
-        assert self.bucket is not None or self.host_buckets or lora_te_cfg, "nothing to train: no LoRA layer matched and no host group given"
+        assert self.bucket is not None or self.host_buckets or lora_te_cfg or pt_cfg, "nothing to train: no LoRA layer matched and no host group given"
         self._lora_state = (_OptState(self.bucket, lr * scale_lr_factor, self.device,
                                       segments=self._segments(self.param_groups, self.bucket, scale_lr_factor, lr))
                             if self.bucket is not None else None)
@@ -211,11 +217,30 @@ class NativeTrainer:
                                            segments=self._segments(te_groups, self.te_bucket, scale_lr_factor, lr))
         elif lora_te_cfg:
             raise ValueError("lora_te_cfg needs the text_encoder module")
+        self.pt_bucket, self._pt_state, self.pt_words = None, None, {}
+        if pt_cfg:
+            from .prompt_tuning import PTBucket, find_hook
+            hook = find_hook(text_encoder) if text_encoder is not None else None
+            if hook is None:
+                raise ValueError("pt_cfg needs a text_encoder carrying an embedding hook (EmbeddingPTHook.hook)")
+            words = []
+            for item in pt_cfg:
+                if item["name"] not in (pt_words or {}):
+                    raise ValueError(f"pt_cfg word {item['name']!r} is not in pt_words")
+                words.append((item["name"], pt_words[item["name"]], item.get("lr", lr) * scale_lr_factor))
+            self.pt_bucket = PTBucket(hook, words)
+            self.pt_words = dict(zip(self.pt_bucket.names, self.pt_bucket.words))
+            self.pt_hook = hook
+            self._pt_state = _OptState(self.pt_bucket, lr, self.device, segments=self.pt_bucket.segments)
+            self._pt_state.weight_decay = pt_weight_decay
+            self._pt_state.clipped = self.te_bucket is not None
+            self._pt_state.no_ema = True
         self.ema_cfg = None
         if ema is not None:
             self.ema_cfg = {**dict(decay_max=0.9997, inv_gamma=1.0, power=2.0 / 3.0), **ema}
             for st in self._states():
-                st.ema = st.bucket.params.clone()
+                if not getattr(st, "no_ema", False):          # (ModelEMA covers the UNet / text encoder, not the words)
+                    st.ema = st.bucket.params.clone()
         for st in self.host_buckets:
             st.bucket.repack()
         self.weight_decay, self.betas, self.eps, self.max_grad_norm = weight_decay, betas, eps, max_grad_norm
@@ -274,7 +299,7 @@ class NativeTrainer:
             if encoder_hidden_states is None:                             # wrapper.py:20: the prompt is encoded inside the step
                 if self.text_encoder is None or prompt_ids is None:
                     raise ValueError("a batch needs encoder_hidden_states, or prompt_ids together with a text_encoder")
-                with torch.set_grad_enabled(self.te_bucket is not None):
+                with torch.set_grad_enabled(self.te_bucket is not None or getattr(self, "pt_bucket", None) is not None):
                     encoder_hidden_states = self.text_encoder(prompt_ids, attention_mask=attn_mask)
             if plugin_input:                                              # wrapper.py:15,25-28: feeders see the batch dict
                 for feeder in getattr(self.unet, "input_feeder", []):
@@ -341,7 +366,8 @@ class NativeTrainer:
 
     def _states(self):
         return (([self._lora_state] if self._lora_state is not None else []) + self.host_buckets +
-                ([self._te_state] if getattr(self, "_te_state", None) is not None else []))
+                ([self._te_state] if getattr(self, "_te_state", None) is not None else []) +
+                ([self._pt_state] if getattr(self, "_pt_state", None) is not None else []))
 
     def all_reduce(self):
         """DDP's exchange for the buckets that are NOT sharded: one all-reduce(SUM) per flat gradient bucket (LoRA: 12 MB)."""
@@ -370,7 +396,7 @@ class NativeTrainer:
             part = torch.stack([st.sumsq for st in sharded]).sum(0)
             self.comm.all_reduce_(part)
             total = part
-        rest = [st.sumsq for st in states if not st.shard]
+        rest = [st.sumsq for st in states if not st.shard and getattr(st, "clipped", True)]
         if rest:
             r = rest[0] if len(rest) == 1 else torch.stack(rest).sum(0)
             total = r if total is None else total + r
@@ -397,14 +423,17 @@ class NativeTrainer:
                 if st.gwire is None:
                     b.grads.zero_()                           # zero_grad of the full bucket (the kernel cleared the slice copy only)
                 continue
+            clipped = getattr(st, "clipped", True)            # prompt-tuning words outside the clip: textual inversion alone
             for (off, n), lr_t, step_t in zip(st.segments, st.lrs, st.steps):
                 K.adamw_clip_fused(b.params[off:off + n], b.grads[off:off + n], st.exp_avg[off:off + n], st.exp_avg_sq[off:off + n],
                                    lr_t, step_t, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
-                                   weight_decay=self.weight_decay, sumsq_t=total, grad_scale=1.0 / self.world,
-                                   max_norm=self.max_grad_norm)
+                                   weight_decay=getattr(st, "weight_decay", self.weight_decay),
+                                   sumsq_t=total if clipped else None, grad_scale=1.0 / self.world,
+                                   max_norm=self.max_grad_norm if clipped else 0.0)
         if self.ema_cfg is not None:           # update_ema (train_ac.py:503,517-521)
             for st in states:
-                K.ema_update(st.ema, st.bucket.params, st.step_count, **self.ema_cfg)
+                if hasattr(st, "ema"):
+                    K.ema_update(st.ema, st.bucket.params, st.step_count, **self.ema_cfg)
         if self.bucket is not None:
             self.bucket.pack()                 # refresh the bf16 LoRA operands for the next forward
         if self.te_bucket is not None:
@@ -416,6 +445,8 @@ class NativeTrainer:
         """{parameter name: EMA tensor} with the parameters' own shapes (what ModelEMA.state_dict() returns, utils/ema.py:46-47)."""
         out = {}
         for st in self._states():
+            if not hasattr(st, "ema"):
+                continue
             b = st.bucket
             named = getattr(b, "named", None)
             if named is None:              # LoraBucket: names from the model
@@ -441,7 +472,10 @@ class NativeTrainer:
         paths = [ckpt_manager.save_model_with_lora(self.unet, self.lora_group, name=name, step=step, model_ema=ema)]
         if self.lora_te_group is not None:     # train_ac.py:529-533: the text encoder's own file
             te_ema = _EMAView(self.ema_state_dict(), self.text_encoder) if self.ema_cfg else None
-            paths.append(ckpt_manager.save_model_with_lora(self.text_encoder, self.lora_te_group, name="text_encoder", step=step, model_ema=te_ema))
+            paths.append(ckpt_manager.save_model_with_lora(self.text_encoder, self.lora_te_group, name="text_encoder", step=step, model_ema=te_ema,
+                                                           exclude_key="emb_ex."))      # train_ac.py:531-533: the words have files of their own
+        if getattr(self, "pt_words", None):    # train_ac.py:542: {word}-{step}.pt, the reference's save_emb layout
+            paths += ckpt_manager.save_embedding(self.pt_words, step, False) or []
         for plugin in self.plugins:
             pema = None
             if ema is not None:             # EMA names of a plugin bucket are relative to the plugin; a whole-model plugin's
@@ -509,6 +543,11 @@ class NativeTrainer:
         Per-dataset ``loss_weight`` (train_ac.py:481, get_loss_weights) scales that batch's loss and gradient.  Returns the
         summed loss (device tensor).  With gradient accumulation the exchange + optimizer step run on every N-th call."""
         data_list = [{**b, "latents": b["latents"].float().contiguous()} for b in data_list]     # the caller's dicts stay untouched
+        if getattr(self, "pt_bucket", None) is not None:     # custom ids without a word: refused here while the batch is still on the host
+            from .prompt_tuning import check_ids
+            for b in data_list:
+                if b.get("prompt_ids") is not None:
+                    check_ids(self.pt_hook, b["prompt_ids"])
         self._micro += 1
         sync = self._micro % self.accum == 0
         early = sync and self._overlap             # this backward sends the early chunks itself

@@ -29,8 +29,9 @@ int hcp_is_emulated(void); /* 0 for the product library */
  * entry points (slabs + ordered reduce instead of fp32 atomics), 152-byte grouped descriptors; earlier in-place argument insertions
  * (ldt on hcp_gemm_lora_bf16 / hcp_gemm_geglu_bwd_bf16, l_lo, ldu / ldt) are covered by the same bump.  3: round 6 — the (hi | lo)
  * residual stream: residual_lo / D_lo on hcp_gemm_bf16 / hcp_gemm_lora_bf16, x_lo / addend_lo / dx_lo on hcp_layernorm_fwd / _bwd; the
- * GEGLU-forward output gact on hcp_gemm_bf16 / hcp_gemm_lora_bf16. */
-#define HCP_ABI_VERSION 3
+ * GEGLU-forward output gact on hcp_gemm_bf16 / hcp_gemm_lora_bf16.  4: prompt tuning — hcp_embedding_pt_fwd_bf16 /
+ * hcp_embedding_pt_bwd_f32 (csrc/embedding.hip). */
+#define HCP_ABI_VERSION 4
 int hcp_abi_version(void);
 /* Device self-check of the fp32 atomic path (no reference counterpart: the reference's sums are torch's).  workgroups x 256 threads add
  * small integers into line[16] and into bucket[i * stride], i < nb (both cleared here first); exact expected values:
@@ -183,6 +184,19 @@ int hcp_vae_latent_sample(const float* moments, const float* Wq, const float* bq
 int hcp_quick_gelu(const void* x, const void* dy, void* out, long n, hcpStream_t stream);   /* dy NULL: forward; else dx */
 int hcp_embedding_bf16(const float* token_table, const long long* ids, const float* position_table, const long long* position_ids,
                        void* out, long n, int C, int L, hcpStream_t stream);
+/* Prompt tuning (EmbeddingPTHook, hcpdiff/models/text_emb_ex.py:33-69, then CLIPTextEmbeddings' position add; csrc/embedding.hip).
+ * ids [B, R*W] int64 (the hook's regrouped layout); custom_map int32 [n_map][2] = (row offset into custom_table [n_custom, C], n_vec)
+ * of token id vocab + i.  Per batch item each id >= vocab with a registered word becomes its n_vec custom rows, rows [1, R*n_word + 1)
+ * of the expanded sequence are cut into R chunks of n_word, and every chunk gets BOS / EOS = token rows of ids[0][0] / ids[0][R*W-1]
+ * (batch item 0, ids clipped to [0, vocab-1]).  out bf16 [B*R, n_word+2, C] = bf16(src_row + position_table[position_ids or j]) in fp32;
+ * src_map int32 [B*R, n_word+2]: >= 0 token row, < 0 custom row -1 - code.  Unregistered ids >= vocab (and negative ids) read the
+ * clipped token row.  Needs R*n_word + 1 <= R*W <= 2048, R*(n_word+2) <= 2048, C % 8 == 0, 16-byte aligned tables. */
+int hcp_embedding_pt_fwd_bf16(const long long* ids, int B, int R, int W, int n_word, const float* token_table, int vocab,
+                              const float* position_table, const long long* position_ids, int n_pos, const float* custom_table,
+                              int n_custom, const int* custom_map, int n_map, void* out, int* src_map, int C, hcpStream_t stream);
+/* grad[k, :] (beta 1: +)= sum over the M rows m with src_map[m] == -1 - k of dX[m, :] (bf16 [M, C]), summed in increasing m by one
+ * workgroup per (k, 256-column slab): no atomics, bit-reproducible.  grad fp32 [n_custom, C]. */
+int hcp_embedding_pt_bwd_f32(const void* dX, const int* src_map, long M, int C, float* grad, int n_custom, int beta, hcpStream_t stream);
 /* per-sample loss weights of the reference's timestep-aware criteria (hcpdiff/loss/min_snr_loss.py): kind 0 MinSNRLoss :21-25,
  * 1 SoftMinSNRLoss :31-35, 2 KDiffMinSNRLoss :39-43, 3 EDMLoss :47-52; snr = acp/(1-acp) as in :14-19.  w: float[B]. */
 int hcp_snr_loss_weight(const long long* timesteps, const float* alphas_cumprod, float* w, int B, int kind, float gamma,
