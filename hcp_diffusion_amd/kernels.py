@@ -89,6 +89,14 @@ def atomics_selfcheck(device, workgroups=2048, nb=4099, stride=37):
 
 
 TRACE = None        # tools/autotune.py: a list collects the (kind, shape...) key of every GEMM-family launch
+# tools/trace_gemm_launches.py / tests/test_gemm_launches.py: a list collects one plain dict per GEMM-family launch — sizes, strides and
+# epilogue flags, enough to rebuild the call at its real shape (tests/gemm_check.py).  None (the default): nothing is recorded.
+LAUNCHES = None
+
+
+def _launch(kind, **d):
+    d["kind"] = kind
+    LAUNCHES.append(d)
 
 
 def _lo_pair(residual, residual_lo, want_lo, M, N, dev):
@@ -117,6 +125,12 @@ def gemm(a, b, *, a2=None, b2=None, bias=None, rowbias=None, rows_per_group=1, r
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32 if out_f32 else BF16, device=a.device)
     assert out.stride(1) == 1
+    if LAUNCHES is not None:
+        _launch("gemm", M=M, N=N, K=K, K2=K2, lda=a.stride(0), ldb=b.stride(0), ldd=out.stride(0),
+                lda2=a2.stride(0) if K2 else 0, ldb2=b2.stride(0) if K2 else 0, ldr=residual.stride(0) if residual is not None else 0,
+                bias=bias is not None, rowbias=rowbias is not None, rows_per_group=rows_per_group if rowbias is not None else 0,
+                residual=residual is not None, residual_lo=residual_lo is not None, want_lo=bool(want_lo), gact=bool(want_gact),
+                alpha=float(alpha), out_f32=out.dtype == torch.float32)
     if bias is not None:
         assert bias.dtype == torch.float32 and bias.numel() == N and bias.is_contiguous()
     if rowbias is not None:
@@ -163,6 +177,10 @@ def gemm_lora(a, b, l, e, *, bias=None, residual=None, want_t=True, residual_lo=
         TRACE.append(("lora", M, N, Kd))
     out = torch.empty((M, N), dtype=BF16, device=a.device)
     ldt = 64 if T_SPLIT else 32
+    if LAUNCHES is not None:
+        _launch("gemm_lora", M=M, N=N, K=Kd, lda=a.stride(0), ldb=b.stride(0), ldd=N, ldt=ldt, want_t=bool(want_t),
+                ldr=residual.stride(0) if residual is not None else 0, bias=bias is not None, residual=residual is not None,
+                residual_lo=residual_lo is not None, want_lo=bool(want_lo), gact=bool(want_gact))
     t = torch.empty((M, ldt), dtype=BF16, device=a.device) if want_t else None
     if bias is not None:
         assert bias.dtype == torch.float32 and bias.numel() == N and bias.is_contiguous()
@@ -189,6 +207,9 @@ def gemm_geglu_bwd(dy, wt, hg, *, l=None, e=None, want_t=True):
     assert wt.shape[1] == C and hg.shape == (M, 2 * Fd) and hg.is_contiguous()
     if TRACE is not None:
         TRACE.append(("lora", M, Fd, C) if l is not None else ("gemm", M, Fd, C, 0))
+    if LAUNCHES is not None:
+        _launch("gemm_geglu_bwd", M=M, N=Fd, K=C, lda=dy.stride(0), ldb=wt.stride(0), ldd=2 * Fd, lora=l is not None,
+                ldt=(64 if T_SPLIT else 32) if l is not None else 0, want_t=bool(want_t) and l is not None)
     dhg = torch.empty((M, 2 * Fd), dtype=BF16, device=dy.device)
     u = None
     if l is not None:
@@ -202,10 +223,10 @@ def gemm_geglu_bwd(dy, wt, hg, *, l=None, e=None, want_t=True):
 
 
 def conv3x3(x1, wp, cout, *, x2=None, stride=1, upsample=False, mode=0, out_hw=None, bias=None, rowbias=None,
-            residual=None, out_f32=False, a2=None, b2=None, pad=1):
+            residual=None, out_f32=False, a2=None, b2=None, pad=1, out=None):
     """3x3 convolution on NHWC bf16. mode 0: forward (wp = [cout][3][3][C1+C2]); mode 1: data gradient
     (x1 = dY [B,Hs,Ws,C1], wp = [cin][3][3][C1], out_hw = spatial dims of the forward input).  pad=0 (forward only): the VAE
-    encoder's asymmetric Downsample2D, F.pad(x, (0,1,0,1)) + padding 0."""
+    encoder's asymmetric Downsample2D, F.pad(x, (0,1,0,1)) + padding 0.  out: optional contiguous [B,Ho,Wo,cout] output buffer."""
     assert x1.dtype == BF16 and x1.dim() == 4 and x1.is_contiguous()
     B, Hs, Ws, C1 = x1.shape
     C2 = 0
@@ -221,7 +242,14 @@ def conv3x3(x1, wp, cout, *, x2=None, stride=1, upsample=False, mode=0, out_hw=N
         Ho, Wo = out_hw
     if TRACE is not None:
         TRACE.append(("conv", mode, B, Hs, Ws, C1, C2, cout, stride, 1 if upsample else 0, Ho, Wo, 1 if a2 is not None else 0))
-    out = torch.empty((B, Ho, Wo, cout), dtype=torch.float32 if out_f32 else BF16, device=x1.device)
+    if LAUNCHES is not None:
+        _launch("conv3x3", M=B * Ho * Wo, N=cout, K=9 * (C1 + C2), K2=32 if a2 is not None else 0, mode=mode, B=B, Hs=Hs, Ws=Ws, C1=C1, C2=C2,
+                Cout=cout, stride=stride, upsample=1 if upsample else 0, pad=pad, Ho=Ho, Wo=Wo, ldd=cout, ldr=cout if residual is not None else 0,
+                bias=bias is not None, rowbias=rowbias is not None, rows_per_group=Ho * Wo if rowbias is not None else 0,
+                residual=residual is not None, out_f32=bool(out_f32))
+    if out is None:
+        out = torch.empty((B, Ho, Wo, cout), dtype=torch.float32 if out_f32 else BF16, device=x1.device)
+    assert out.dtype == (torch.float32 if out_f32 else BF16) and out.is_contiguous() and tuple(out.shape) == (B, Ho, Wo, cout)
     if residual is not None:
         assert residual.dtype == BF16 and residual.is_contiguous() and residual.numel() == out.numel()
     if rowbias is not None:
@@ -246,6 +274,8 @@ def wgrad_linear(dy, x, dw):
     M, N = dy.shape
     K = x.shape[1]
     assert tuple(dw.shape) == (N, K)
+    if LAUNCHES is not None:
+        _launch("wgrad_linear", M=M, N=N, K=K, ldy=dy.stride(0), ldx=x.stride(0), ldw=dw.stride(0))
     ws = _workspace(x)
     _chk(lib().hcp_wgrad_linear_bf16(_p(dy), dy.stride(0), _p(x), x.stride(0), _p(dw), dw.stride(0), M, N, K, _p(ws), ws.numel(),
                                      _stream(x)), "hcp_wgrad_linear_bf16")
@@ -268,6 +298,9 @@ def wgrad_conv3x3(dy, x1, dw, *, x2=None, stride=1, upsample=False, cout=None, c
     assert dw.numel() == cout * 9 * cw and cw <= C1 + C2
     ws = _workspace(x1)
     assert col0 % 8 == 0 and col0 + (cout + 7) // 8 * 8 <= ldy
+    if LAUNCHES is not None:
+        _launch("wgrad_conv3x3", M=B * Ho * Wo, N=cout, K=9 * (C1 + C2), B=B, Hs=Hs, Ws=Ws, C1=C1, C2=C2, Cout=cout, Cw=cw, stride=stride,
+                upsample=1 if upsample else 0, Ho=Ho, Wo=Wo, ldy=ldy, col0=col0)
     dyp = ctypes.c_void_p(dy.data_ptr() + 2 * col0)
     _chk(lib().hcp_wgrad_conv3x3_bf16(dyp, ldy, _p(x1), C1, _p(x2), C2, _p(dw), cw, B, Hs, Ws, Ho, Wo, cout, stride,
                                       1 if upsample else 0, _p(ws), ws.numel(), _stream(x1)), "hcp_wgrad_conv3x3_bf16")

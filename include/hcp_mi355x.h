@@ -140,7 +140,9 @@ int hcp_nhwc_to_nchw_f32(const float* src, float* dst, int B, int C, int HW, int
 int hcp_upsample2x_bwd(const void* dup, void* dx, int B, int H, int W, int C, hcpStream_t stream);
 
 /* ---- host-layer weight gradients (full fine-tuning: cfgs/train/examples/DreamBooth.yaml:6-10 trains every UNet
- * parameter; autograd's dW of nn.Linear / nn.Conv2d [ext]).  fp32 `+=` into the gradient buffer (atomics). ---- */
+ * parameter; autograd's dW of nn.Linear / nn.Conv2d [ext]).  fp32 `+=` into the gradient buffer: token-split partial sums go to
+ * workspace slabs that a reduce kernel adds in split order (no atomics, bit-reproducible); only hcp_colsum_bf16 adds with fp32
+ * atomics. ---- */
 /* dW[N,K] += dY[M,N]^T X[M,K]; workspace = optional fp32 scratch for token-split partial sums */
 int hcp_wgrad_linear_bf16(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int M, int N, int K,
                           float* workspace, size_t workspace_bytes, hcpStream_t stream);

@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import gemm_check as GC
 from hcp_diffusion_amd import kernels as K
 
 BF = torch.bfloat16
@@ -50,8 +51,11 @@ def test_narrow_tile_plain_gemm(tbackend, ring):
             L.hcp_debug_set_gemm_config(force(NARROW, split))
             out = K.gemm(to(a), to(b), a2=to(a2), b2=to(b2), bias=to(bias), residual=to(res))
             assert relerr(out, ref) < 1e-2, split
+            ops = dict(a=to(a), b=to(b), a2=to(a2), b2=to(b2), bias=to(bias), residual=to(res))
+            GC.check(GC.desc("gemm", M=M, N=N, K=Kd, K2=32, bias=True, residual=True), ops, {"out": out})
             o32 = K.gemm(to(a), to(b), bias=to(bias), out_f32=True)
             assert relerr(o32, a.float() @ b.float().T + bias) < 1e-5, split
+            GC.check(GC.desc("gemm", M=M, N=N, K=Kd, bias=True, out_f32=True), ops, {"out": o32})
     finally:
         _reset(L)
 
@@ -73,6 +77,8 @@ def test_narrow_tile_fused_lora(tbackend, ring):
         out, t = K.gemm_lora(to(a), to(b), to(l), to(e), bias=to(bias), residual=to(res))
         assert relerr(out, ref) < 1e-2
         assert relerr(t_full(t), t_ref) < (1e-4 if K.T_SPLIT else 1e-2)
+        GC.check(GC.desc("gemm_lora", M=M, N=N, K=Kd, ldt=t.shape[1], bias=True, residual=True),
+                 dict(a=to(a), b=to(b), l=to(l), e=to(e), bias=to(bias), residual=to(res)), {"out": out, "t": t})
     finally:
         _reset(L)
 
@@ -112,6 +118,11 @@ def test_narrow_tile_epilogues_agree(tbackend):
     ref = 0.5 * (a.float() @ b.float().T + a2.float() @ b2.float().T) + bias + rb.repeat_interleave(rpg, 0)[:M] + hi.float()
     assert relerr(tile[0], ref) < 1e-2
     assert relerr(tile[1].float() + tile[2].float(), a.float() @ b.float().T + bias + hi.float() + lo.float()) < 1e-4
+    ops = dict(a=a, b=b, a2=a2, b2=b2, bias=bias, rowbias=rb, residual=hi, residual_lo=lo, l=l, e=e)
+    GC.check(GC.desc("gemm", M=M, N=N, K=Kd, K2=32, bias=True, rowbias=True, rows_per_group=rpg, residual=True, alpha=0.5), ops, {"out": tile[0]})
+    GC.check(GC.desc("gemm", M=M, N=N, K=Kd, bias=True, residual=True, residual_lo=True, want_lo=True), ops, {"out": tile[1], "out_lo": tile[2]})
+    GC.check(GC.desc("gemm_lora", M=M, N=N, K=Kd, ldt=tile[5].shape[1], bias=True, residual=True, residual_lo=True, want_lo=True), ops,
+             {"out": tile[3], "out_lo": tile[4], "t": tile[5]})
 
 
 @pytest.mark.parametrize("lora", [False, True])
@@ -131,7 +142,7 @@ def test_narrow_tile_geglu_falls_back(tbackend, lora):
     try:
         L.hcp_debug_set_gemm_loaders(8 + 3); L.hcp_debug_set_gemm_config(force(NARROW))
         if lora:
-            (o, ga), _ = K.gemm_lora(to(a), to(b), to(l), to(e), bias=to(bias), want_gact=True)
+            (o, ga), t = K.gemm_lora(to(a), to(b), to(l), to(e), bias=to(bias), want_gact=True)
         else:
             o, ga = K.gemm(to(a), to(b), bias=to(bias), want_gact=True)
     finally:
@@ -139,6 +150,11 @@ def test_narrow_tile_geglu_falls_back(tbackend, lora):
     assert relerr(o, hg) < 1e-2
     two_pass = F.gelu(o.float().cpu()[:, Fd:]) * o.float().cpu()[:, :Fd]
     assert relerr(ga, two_pass) < 1e-2
+    ops = dict(a=to(a), b=to(b), l=to(l), e=to(e), bias=to(bias))
+    if lora:
+        GC.check(GC.desc("gemm_lora", M=M, N=2 * Fd, K=Kd, ldt=t.shape[1], bias=True, gact=True), ops, {"out": o, "gact": ga, "t": t})
+    else:
+        GC.check(GC.desc("gemm", M=M, N=2 * Fd, K=Kd, bias=True, gact=True), ops, {"out": o, "gact": ga})
 
 
 # the SD1.5 shapes (batch 4) whose dispatch-table entries moved to the narrow tile: (fused-LoRA?, M, N, K, K2)

@@ -13,6 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import gemm_check as GC
 from hcp_diffusion_amd import kernels as K
 
 BF = torch.bfloat16
@@ -59,8 +60,12 @@ def test_gemm(backend, case):
     out = K.gemm(to(a), to(b), a2=to(a2) if K2 else None, b2=to(b2) if K2 else None, bias=to(bias), rowbias=to(rb),
                  rows_per_group=rpg, residual=to(res), alpha=0.5, out_f32=True)
     assert relerr(out, ref) < 2e-5
+    ops = dict(a=to(a), b=to(b), bias=to(bias), rowbias=to(rb), residual=to(res), **(dict(a2=to(a2), b2=to(b2)) if K2 else {}))
+    GC.check(GC.desc("gemm", M=M, N=N, K=Kd, K2=K2, bias=True, rowbias=True, rows_per_group=rpg, residual=True, alpha=0.5, out_f32=True),
+             ops, {"out": out})
     out16 = K.gemm(to(a), to(b))
     assert relerr(out16, a.float() @ b.float().T) < 1e-2
+    GC.check(GC.desc("gemm", M=M, N=N, K=Kd), ops, {"out": out16})
 
 
 CONV_CASES_EMU = [  # B, C1, C2, H, W, Cout, stride, up
@@ -89,6 +94,9 @@ def test_conv3x3_forward(backend, case):
     out = K.conv3x3(to(nhwc(x1)), to(wp), Cout, x2=to(nhwc(x2)) if C2 else None, stride=stride, upsample=bool(up), bias=to(bias),
                     rowbias=to(temb), residual=to(nhwc(res)), out_f32=True)
     assert relerr(out.permute(0, 3, 1, 2), ref) < 2e-5
+    ops = dict(x1=to(nhwc(x1)), wp=to(wp), bias=to(bias), rowbias=to(temb), residual=to(nhwc(res)), **(dict(x2=to(nhwc(x2))) if C2 else {}))
+    GC.check(GC.desc("conv3x3", B=B, Hs=H, Ws=W, C1=C1, C2=C2, Cout=Cout, stride=stride, upsample=up, Ho=ref.shape[2], Wo=ref.shape[3],
+                     bias=True, rowbias=True, residual=True, out_f32=True), ops, {"out": out})
 
 
 @pytest.mark.parametrize("B,C,H,W,Cout", [(2, 16, 8, 6, 8), (1, 8, 6, 6, 24), (2, 128, 64, 64, 128), (1, 256, 128, 128, 256), (2, 512, 32, 32, 512)])
@@ -103,6 +111,8 @@ def test_conv3x3_stride2_asymmetric_pad(backend, B, C, H, W, Cout):
     out = K.conv3x3(backend.to(nhwc(x)), backend.to(w.permute(0, 2, 3, 1).contiguous()), Cout, stride=2, pad=0, bias=backend.to(bias), out_f32=True)
     assert tuple(out.shape) == (B, H // 2, W // 2, Cout)
     assert relerr(out.permute(0, 3, 1, 2), ref) < 2e-5
+    GC.check(GC.desc("conv3x3", B=B, Hs=H, Ws=W, C1=C, Cout=Cout, stride=2, pad=0, Ho=H // 2, Wo=W // 2, bias=True, out_f32=True),
+             dict(x1=backend.to(nhwc(x)), wp=backend.to(w.permute(0, 2, 3, 1).contiguous()), bias=backend.to(bias)), {"out": out})
 
 
 DGRAD_CASES_EMU = [(2, 16, 6, 5, 24, 1), (1, 8, 8, 8, 16, 2), (1, 8, 7, 5, 16, 2)]
@@ -124,6 +134,8 @@ def test_conv3x3_dgrad(backend, case):
     wd = w.permute(1, 2, 3, 0).contiguous()
     out = K.conv3x3(to(nhwc(dy)), to(wd), Cin, mode=1, stride=stride, out_hw=(H, W), out_f32=True)
     assert relerr(out.permute(0, 3, 1, 2), x.grad) < 2e-5
+    GC.check(GC.desc("conv3x3", mode=1, B=B, Hs=y.shape[2], Ws=y.shape[3], C1=Cout, Cout=Cin, stride=stride, Ho=H, Wo=W, out_f32=True),
+             dict(x1=to(nhwc(dy)), wp=to(wd)), {"out": out})
 
 
 ATTN_CASES_EMU = [  # B, H, Nq, Nk, D
@@ -920,6 +932,7 @@ def test_wgrad_linear(tbackend, case, wx):
     finally:
         K.lib().hcp_debug_set_wgrad_tile(0)
     assert relerr(dw, ref) < 3e-5 * max(1.0, math.sqrt(M / 256))
+    GC.check(GC.desc("wgrad_linear", M=M, N=N, K=Kd), dict(dy=to(dy)[:, :N], x=to(x), dw0=to(dw0)), {"out": dw})
 
 
 WGC_CASES_EMU = [  # B, C1, C2, H, W, Cout, stride, up, Cw
@@ -953,6 +966,9 @@ def test_wgrad_conv3x3(backend, case):
     dw = to(dw0.clone())
     K.wgrad_conv3x3(to(dyp), to(nhwc(x1)), dw, x2=to(nhwc(x2)) if C2 else None, stride=stride, upsample=bool(up), cout=Cout)
     assert relerr(dw, ref) < 3e-5 * max(1.0, math.sqrt(B * y.shape[2] * y.shape[3] / 256))
+    ops = dict(dy=to(dyp), x1=to(nhwc(x1)), dw0=to(dw0), **(dict(x2=to(nhwc(x2))) if C2 else {}))
+    GC.check(GC.desc("wgrad_conv3x3", B=B, Hs=H, Ws=W, C1=C1, C2=C2, Cout=Cout, Cw=Cw, stride=stride, upsample=up, Ho=y.shape[2],
+                     Wo=y.shape[3], ldy=ldy), ops, {"out": dw})
 
 
 @pytest.mark.parametrize("M,N,rpg", [(70, 8, None), (256, 72, 64), (1000, 320, None), (128, 16, 32)])

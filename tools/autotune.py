@@ -17,14 +17,12 @@ sys.path.insert(0, ROOT)
 from hcp_diffusion_amd import kernels as K
 from hcp_diffusion_amd import _lib
 K._set_backend_for_tests(_lib.load_tools())      # tuning build: the hcp_debug_* hooks do not exist in the product library
-from hcp_diffusion_amd.trainer import NativeTrainer
-from hcp_diffusion_amd.unet import SDXL_CONFIG, NativeUNet2DConditionModel
+from workloads import BATCH, PATS, setup  # noqa: E402,F401  (PATS: tools/tune_loaders.py)
 
 BF = torch.bfloat16
 dev = torch.device("cuda:0")
 CFG_NAMES = ["128x128", "128x64", "64x64", "128x160", "64x160", "256x128", "256x160", "128x320", "128x160w8s3", "128x160w4s3", "256x160w8s3",
              "128x320w16", "256x160w16", "128x160w8", "64x160w8", "128x128w8"]
-PATS = [r"re:.*\.attn.?$", r"re:.*\.ff$"]
 
 
 def timeit(fn, iters=10, warm=2):
@@ -59,34 +57,7 @@ def rnd(*s):
 
 
 def trace(workload, B):
-    sdxl = workload == "sdxl"
-    with torch.device("meta"):
-        unet = NativeUNet2DConditionModel(**SDXL_CONFIG) if sdxl else NativeUNet2DConditionModel()
-    unet = unet.to_empty(device=dev)
-    with torch.no_grad():
-        for n, p in unet.named_parameters():
-            p.normal_(0, 0.02) if p.dim() > 1 else p.fill_(1.0 if n.endswith("weight") else 0.0)
-    kw = {}
-    if workload == "dreambooth":
-        tr = NativeTrainer(unet, None, train_cfg=[dict(layers=[""], lr=1e-6)])
-    elif workload == "controlnet":
-        from hcp_diffusion_amd.controlnet import make_controlnet
-        plug = make_controlnet(unet)
-        with torch.no_grad():
-            for m in list(plug.controlnet_down_blocks) + [plug.controlnet_mid_block, plug.cond_head[-1]]:
-                m.weight.normal_(0, 0.02)
-        tr = NativeTrainer(unet, None, plugins=[(plug, 1e-4)])
-        kw["plugin_input"] = dict(cond=torch.rand(B, 3, 512, 512, device=dev))
-    else:
-        tr = NativeTrainer(unet, [dict(layers=PATS, rank=16 if sdxl else 8)])
-        with torch.no_grad():
-            for blk in tr.bucket.blocks:
-                blk.layer.W_up.normal_(0, 0.02)
-        tr.bucket.pack()
-    hw, cd = (128, 2048) if sdxl else (64, 768)
-    lat = torch.randn(B, 4, hw, hw, device=dev); ehs = torch.randn(B, 77, cd, device=dev).to(BF)
-    if sdxl:
-        kw["added_cond_kwargs"] = dict(text_embeds=torch.randn(B, 1280, device=dev), time_ids=torch.tensor([[1024.0, 1024, 0, 0, 1024, 1024]] * B, device=dev))
+    tr, lat, ehs, kw = setup(workload, B, dev)
     tr.train_one_step(lat, ehs, **kw)          # warm-up (lazy packing)
     K.lib().hcp_debug_gemm_table_stats(None, None)
     K.TRACE = []
@@ -97,7 +68,7 @@ def trace(workload, B):
     h, m = ctypes.c_long(), ctypes.c_long()
     K.lib().hcp_debug_gemm_table_stats(ctypes.byref(h), ctypes.byref(m))
     print(f"dispatch table during the traced step(s): {h.value} hits, {m.value} misses", flush=True)
-    del tr, unet
+    del tr
     torch.cuda.empty_cache()
     return keys
 
@@ -128,7 +99,7 @@ def choose(res):
 
 def main():
     workload = sys.argv[1]
-    B = int(sys.argv[2]) if len(sys.argv) > 2 else {"sdxl": 2, "dreambooth": 2}.get(workload, 4)
+    B = int(sys.argv[2]) if len(sys.argv) > 2 else BATCH[workload]
     keys = trace(workload, B)
     print(f"{workload} bs{B}: {len(keys)} distinct GEMM-family shapes, {sum(keys.values())} launches per step", flush=True)
     out = []
