@@ -90,7 +90,8 @@ def atomics_selfcheck(device, workgroups=2048, nb=4099, stride=37):
 
 TRACE = None        # tools/autotune.py: a list collects the (kind, shape...) key of every GEMM-family launch
 # tools/trace_gemm_launches.py / tests/test_gemm_launches.py: a list collects one plain dict per GEMM-family launch — sizes, strides and
-# epilogue flags, enough to rebuild the call at its real shape (tests/gemm_check.py).  None (the default): nothing is recorded.
+# epilogue flags, enough to rebuild the call at its real shape (tests/gemm_check.py); tools/trace_attention_launches.py /
+# tests/test_attention_launches.py: the same for attention_fwd / attention_bwd (tests/attn_check.py).  None (the default): nothing is recorded.
 LAUNCHES = None
 
 
@@ -327,6 +328,20 @@ def _key_bias(key_bias, B, Nk):
     return key_bias, key_bias.stride(0)
 
 
+def _attn_desc(q, k, v, B, H, Nq, Nk, D, scale, kbt, kbs, causal, pre):
+    """The recorded form of one attention launch: sizes, the batch / row strides of q, k, v (the gradients share them) and the layout —
+    'qkv': q | k | v are the column thirds of one [B, N, 3C] buffer, 'q+kv': k | v are neighbouring column slices of one buffer (the joint
+    K/V projection of every cross-attention layer, or one layer's [B, Nk, 2C]), else 'separate'.  The scale is recorded when it is not
+    the default D^-0.5."""
+    C = H * D
+    e = q.element_size()
+    kv = k.stride() == v.stride() and v.data_ptr() - k.data_ptr() == C * e and k.stride(1) >= 2 * C
+    qkv = kv and q.stride() == k.stride() and k.data_ptr() - q.data_ptr() == C * e and q.stride(1) >= 3 * C
+    return dict(B=B, H=H, Nq=Nq, Nk=Nk, D=D, q_bs=q.stride(0), q_rs=q.stride(1), k_bs=k.stride(0), k_rs=k.stride(1), v_bs=v.stride(0),
+                v_rs=v.stride(1), layout="qkv" if qkv else "q+kv" if kv else "separate", key_bias=kbt is not None, kb_bs=kbs,
+                causal=bool(causal), prescaled=bool(pre), scale=0.0 if abs(scale * math.sqrt(D) - 1.0) < 1e-6 else float(scale))
+
+
 def attention_fwd(q, k, v, heads, scale=None, key_bias=None, causal=False, q_prescaled=False):
     """q [B,Nq,H*d], k/v [B,Nk,H*d] (views with arbitrary batch/row strides allowed) -> (o [B,Nq,H*d], lse [B,H,Nq]).
     key_bias: optional fp32 [B,Nk] added to the scaled scores (additive key mask); causal: key k visible to query q iff k <= q;
@@ -339,6 +354,8 @@ def attention_fwd(q, k, v, heads, scale=None, key_bias=None, causal=False, q_pre
     lse = torch.empty((B, heads, Nq), dtype=torch.float32, device=q.device)
     qb, qr = _attn_strides(q); kb, kr = _attn_strides(k); vb, vr = _attn_strides(v); ob, orr = _attn_strides(o)
     kbt, kbs = _key_bias(key_bias, B, Nk)
+    if LAUNCHES is not None:
+        _launch("attn_fwd", **_attn_desc(q, k, v, B, heads, Nq, Nk, D, scale, kbt, kbs, causal, q_prescaled))
     _chk(lib().hcp_attention_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), B, heads, Nq, Nk, D, qb, qr, kb, kr, vb, vr, ob, orr,
                                  float(scale), _p(kbt), kbs, (1 if causal else 0) | (2 if q_prescaled else 0), _stream(q)), "hcp_attention_fwd")
     return o, lse
@@ -362,6 +379,8 @@ def attention_bwd(q, k, v, o, do, lse, heads, scale=None, out=None, key_bias=Non
     qb, qr = _attn_strides(q); kb, kr = _attn_strides(k); vb, vr = _attn_strides(v); ob, orr = _attn_strides(o)
     ws = _workspace(q)
     kbt, kbs = _key_bias(key_bias, B, Nk)
+    if LAUNCHES is not None:
+        _launch("attn_bwd", **_attn_desc(q, k, v, B, heads, Nq, Nk, D, scale, kbt, kbs, causal, q_prescaled))
     _chk(lib().hcp_attention_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, heads,
                                  Nq, Nk, D, qb, qr, kb, kr, vb, vr, ob, orr, float(scale), _p(kbt), kbs,
                                  (1 if causal else 0) | (2 if q_prescaled else 0), _p(ws),

@@ -452,9 +452,10 @@ def describe(desc):
     return json.dumps({k: v for k, v in desc.items() if v not in (False, 0) or k in ("M", "N", "K")}, sort_keys=True)
 
 
-def compare(desc, items, base=None, cols=None):
+def compare(desc, items, base=None, cols=None, describe=describe):
     """|got - ref| <= bound at every element (NaN fails); the gap columns of `base` beyond `cols` still hold the sentinel.
-    Returns the worst err / bound; raises AssertionError naming the descriptor and the worst element."""
+    Returns the worst err / bound; raises AssertionError naming the descriptor and the worst element (row / col, or the axes an item
+    names in `dims`: tests/attn_check.py gives batch / row / head / col)."""
     worst = 0.0
     for it in items:
         err = (it.got - it.ref).abs()
@@ -467,9 +468,13 @@ def compare(desc, items, base=None, cols=None):
         if bool(bad.any()):
             ncols = it.ref.shape[-1]
             row, col = divmod(i, ncols) if it.ref.dim() == 2 else (i // ncols, i % ncols)
+            where = f"row {row} col {col}"
+            if getattr(it, "dims", None):
+                idx = [int(x) for x in torch.unravel_index(torch.tensor(i), it.ref.shape)]
+                where = " ".join(f"{n} {x}" for n, x in zip(it.dims, idx))
             g, rf, b = float(it.got.reshape(-1)[i]), float(it.ref.reshape(-1)[i]), float(it.bound.reshape(-1)[i])
-            raise AssertionError(f"{it.name} of {describe(desc)}: {int(bad.sum())} elements outside the float64 bound; worst at row {row} "
-                                 f"col {col}: got {g:.9g} ref {rf:.9g} err {abs(g - rf):.3g} bound {b:.3g} (ratio {r:.3g})")
+            raise AssertionError(f"{it.name} of {describe(desc)}: {int(bad.sum())} elements outside the float64 bound; worst at {where}"
+                                 f": got {g:.9g} ref {rf:.9g} err {abs(g - rf):.3g} bound {b:.3g} (ratio {r:.3g})")
         worst = max(worst, r)
     if base is not None and base.shape[1] > cols:
         gap = base[:, cols:]

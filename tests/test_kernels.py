@@ -13,6 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import attn_check as AC
 import gemm_check as GC
 from hcp_diffusion_amd import kernels as K
 
@@ -145,6 +146,16 @@ ATTN_CASES_GPU = ATTN_CASES_EMU + [(4, 8, 4096, 4096, 40), (4, 8, 4096, 77, 40),
                                    (4, 8, 256, 256, 160), (4, 8, 256, 77, 160), (4, 8, 64, 64, 160), (2, 10, 4096, 4096, 64)]
 
 
+def attn_check(H, q, k, v, o, lse, do=None, grads=None, key_bias=None, causal=False, prescaled=False):
+    """the element-wise float64 gate (tests/attn_check.py) on a hand-built call: tensors on the backend's device, as passed to the wrapper."""
+    B, Nq, C = q.shape
+    kw = dict(B=B, H=H, Nq=Nq, Nk=k.shape[1], D=C // H, key_bias=key_bias is not None, causal=causal, prescaled=prescaled)
+    ops = dict(q=q, k=k, v=v, **({"key_bias": key_bias} if key_bias is not None else {}))
+    AC.check(AC.desc("attn_fwd", **kw), ops, dict(o=o, lse=lse))
+    if grads is not None:
+        AC.check(AC.desc("attn_bwd", **kw), dict(ops, do=do), dict(o=o, lse=lse, dq=grads[0], dk=grads[1], dv=grads[2]))
+
+
 def test_attention_additive_key_mask(backend):
     """encoder_attention_mask path: fp32 [B,Nk] bias added to the scaled scores of every head / query, fwd + all gradients."""
     B, H, Nq, Nk, D = 2, 2, 70, 80, 40
@@ -165,6 +176,7 @@ def test_attention_additive_key_mask(backend):
     dq, dk, dv = K.attention_bwd(to(q), to(k), to(v), o, to(do), lse, H, key_bias=to(bias))
     assert relerr(dq, qr.grad) < 2e-2 and relerr(dk, kr.grad) < 2e-2 and relerr(dv, vr.grad) < 2e-2
     assert dk.cpu().float()[0, 50:].abs().max().item() < 1e-6          # masked keys receive no gradient
+    attn_check(H, to(q), to(k), to(v), o, lse, to(do), (dq, dk, dv), key_bias=to(bias))
 
 
 @pytest.mark.parametrize("B,H,N,D,with_bias", [(2, 2, 77, 64, False), (1, 1, 150, 40, True), (2, 12, 77, 64, False), (1, 20, 77, 64, True), (2, 4, 300, 80, False)])
@@ -196,6 +208,7 @@ def test_attention_causal(backend, B, H, N, D, with_bias):
     assert relerr(o[:, 0], v[:, 0]) < 1e-2                                                    # query 0 sees only key 0
     dq, dk, dv = K.attention_bwd(to(q), to(k), to(v), o, to(do), lse, H, key_bias=kb, causal=True)
     assert relerr(dq, qr.grad) < 2e-2 and relerr(dk, kr.grad) < 2e-2 and relerr(dv, vr.grad) < 2e-2
+    attn_check(H, to(q), to(k), to(v), o, lse, to(do), (dq, dk, dv), key_bias=kb, causal=True)
     o2, _ = K.attention_fwd(to(q), to(k), to(v), H, key_bias=kb)
     assert relerr(o2, o_ref) > 5e-2                                                          # the mask matters
 
@@ -231,6 +244,7 @@ def test_attention_fwd_bwd(backend, case):
     assert (lse.cpu() - lse_ref).abs().max().item() < 2e-2
     dq, dk, dv = K.attention_bwd(to(q), to(k), to(v), o, to(do), lse, H)
     assert relerr(dq, dq_ref) < 2e-2 and relerr(dk, dk_ref) < 2e-2 and relerr(dv, dv_ref) < 2e-2
+    attn_check(H, to(q), to(k), to(v), o, lse, to(do), (dq, dk, dv))
 
 
 def test_attention_query_split_dkv_clears_its_own_accumulators(tbackend):
@@ -251,6 +265,8 @@ def test_attention_query_split_dkv_clears_its_own_accumulators(tbackend):
             dq, dk, dv = K.attention_bwd(to(q), to(k), to(v), o, to(do), lse, H)
             assert torch.isfinite(dk.float()).all() and torch.isfinite(dv.float()).all()
             assert relerr(dq, dq_ref) < 2e-2 and relerr(dk, dk_ref) < 2e-2 and relerr(dv, dv_ref) < 2e-2
+            assert AC.workspace_written(o)                                  # the split is real: its first slab lies in the workspace
+        attn_check(H, to(q), to(k), to(v), o, lse, to(do), (dq, dk, dv))
     finally:
         K.lib().hcp_debug_set_attention_config(-1)
 
@@ -309,6 +325,7 @@ def test_attention_rows_per_wave_variants(tbackend, cfg):
         K.lib().hcp_debug_set_attention_config(-1)
     assert relerr(o, o_ref) < 1e-2 and (lse.cpu() - lse_ref).abs().max().item() < 2e-2
     assert relerr(dq, dq_ref) < 2e-2 and relerr(dk, dk_ref) < 2e-2 and relerr(dv, dv_ref) < 2e-2
+    attn_check(H, to(q), to(k), to(v), o, lse, to(do), (dq, dk, dv))
 
 
 @pytest.mark.parametrize("shape", [(1, 2, 150, 200, 40), (2, 1, 64, 77, 80), (1, 1, 100, 130, 64)])
@@ -328,6 +345,7 @@ def test_attention_prescaled_q(backend, shape):
     assert relerr(o, o_ref) < 1e-2 and (lse.cpu() - lse_ref).abs().max().item() < 2e-2
     dq, dk, dv = K.attention_bwd(to(qs), to(k), to(v), o, to(do), lse, H, q_prescaled=True)
     assert relerr(dq.float() * c, dq_ref) < 2e-2 and relerr(dk, dk_ref) < 2e-2 and relerr(dv, dv_ref) < 2e-2
+    attn_check(H, to(qs), to(k), to(v), o, lse, to(do), (dq, dk, dv), prescaled=True)
     with pytest.raises(RuntimeError):
         K.attention_fwd(to(qs), to(k), to(v), H, key_bias=to(torch.zeros(B, Nk)), q_prescaled=True)
 
@@ -365,6 +383,7 @@ def test_attention_lsum_overflow_rerun(backend, mode, prescaled):
     dq, dk, dv = K.attention_bwd(to(qs), to(k), to(v), o, to(do), lse, H, q_prescaled=prescaled)
     dqs = dq.float() * c if prescaled else dq
     assert relerr(dqs, dq_ref) < 2e-2 and relerr(dk, dk_ref) < 2e-2 and relerr(dv, dv_ref) < 2e-2
+    attn_check(H, to(qs), to(k), to(v), o, lse, to(do), (dq, dk, dv), prescaled=prescaled)     # (the checker's own operands avoid the re-run)
 
 
 def test_attention_strided_qkv(backend):
@@ -377,6 +396,50 @@ def test_attention_strided_qkv(backend):
     dq = backend.to(qkv)
     o, _ = K.attention_fwd(dq[..., :H * D], dq[..., H * D:2 * H * D], dq[..., 2 * H * D:], H)
     assert relerr(o, o_ref) < 1e-2
+    # forward and backward, B = 2, both packed layouts of ops._AttentionPackedFn: q | k | v thirds of one [B, N, 3C + gap] buffer, and
+    # q plus k | v inside a wider joint buffer; batch strides with a gap row; dq / dk / dv through out= into slices of sentinel-filled
+    # buffers whose neighbouring columns must stay untouched (tests/attn_check.py)
+    C = H * D
+    for kw in (dict(layout="qkv", Nq=N, Nk=N, q_rs=3 * C + 8, k_rs=3 * C + 8, v_rs=3 * C + 8, q_bs=(N + 1) * (3 * C + 8),
+                    k_bs=(N + 1) * (3 * C + 8), v_bs=(N + 1) * (3 * C + 8)),
+               dict(layout="q+kv", Nq=N, Nk=77, q_bs=(N + 2) * C, k_rs=2 * C + 320, v_rs=2 * C + 320, k_bs=78 * (2 * C + 320),
+                    v_bs=78 * (2 * C + 320))):
+        d = AC.desc("attn_bwd", B=2, H=H, D=D, **kw)
+        ops = AC.make_operands(d, backend.device)
+        assert not ops["k"].is_contiguous() and ops["k"].stride(0) > ops["k"].shape[1] * ops["k"].stride(1)
+        outs = AC.run(d, ops)
+        AC.check(dict(d, kind="attn_fwd"), ops, outs)
+        AC.check(d, ops, outs)
+
+
+def test_attention_key_bias_batch_stride(backend):
+    """key_bias as a non-contiguous-batch view (stride(0) > Nk; the columns beyond Nk hold values that would change the result), on
+    packed q + k|v, forward and backward: the 8-wave masked forward and the query-split masked dK / dV at the SD1.5 shape on the GPU."""
+    B, H, Nq, Nk, D = (4, 8, 4096, 77, 40) if backend.is_gpu else (2, 2, 150, 77, 40)
+    C = H * D
+    d = AC.desc("attn_bwd", B=B, H=H, Nq=Nq, Nk=Nk, D=D, layout="q+kv", k_rs=2 * C + 64, v_rs=2 * C + 64, k_bs=Nk * (2 * C + 64),
+                v_bs=Nk * (2 * C + 64), key_bias=True, kb_bs=Nk + 19)
+    ops = AC.make_operands(d, backend.device)
+    assert ops["key_bias"].stride(0) == Nk + 19 and tuple(ops["key_bias"].shape) == (B, Nk)
+    outs = AC.run(d, ops)
+    AC.check(dict(d, kind="attn_fwd"), ops, outs)
+    AC.check(d, ops, outs)
+
+
+def test_attention_rows_with_every_visible_key_masked(backend):
+    """causal + key bias -10000 on keys 0..4 of batch row 0: queries 0..4 see only masked keys (their softmax is the plain softmax of
+    the scores over those keys: a common -10000 cancels), queries 5.. of the same workgroup see unmasked ones.  Finite lse near
+    -10000, finite gradients, every element against float64 — no special case in the expected values."""
+    B, H, N, D = (2, 12, 77, 64) if backend.is_gpu else (2, 2, 70, 64)
+    torch.manual_seed(11)
+    q, k, v, do = rnd(B, N, H * D), rnd(B, N, H * D), rnd(B, N, H * D), rnd(B, N, H * D)
+    bias = torch.zeros(B, N); bias[0, :5] = -10000.0; bias[1, 7] = -10000.0
+    to = backend.to
+    o, lse = K.attention_fwd(to(q), to(k), to(v), H, key_bias=to(bias), causal=True)
+    dq, dk, dv = K.attention_bwd(to(q), to(k), to(v), o, to(do), lse, H, key_bias=to(bias), causal=True)
+    assert all(torch.isfinite(t.float()).all() for t in (o, lse, dq, dk, dv))
+    assert (lse[0, :, :5].cpu() < -9000).all() and (lse[0, :, 5:].cpu() > -100).all()
+    attn_check(H, to(q), to(k), to(v), o, lse, to(do), (dq, dk, dv), key_bias=to(bias), causal=True)
 
 
 GN_CASES_EMU = [(2, 8, 8, 64, True, 1e-5), (1, 5, 7, 320, False, 1e-6), (2, 4, 4, 96, True, 1e-5),

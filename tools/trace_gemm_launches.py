@@ -17,6 +17,7 @@ from hcp_diffusion_amd import kernels as K  # noqa: E402
 from workloads import BATCH, setup  # noqa: E402
 
 FIXTURE = os.path.join(ROOT, "tests", "golden", "gemm_launches.json")
+KINDS = ("gemm", "gemm_lora", "gemm_geglu_bwd", "conv3x3", "wgrad_linear", "wgrad_conv3x3")     # the attention kinds: tools/trace_attention_launches.py
 
 
 def trace_workload(workload, dev="cuda:0"):
@@ -32,6 +33,8 @@ def trace_workload(workload, dev="cuda:0"):
         K.LAUNCHES = None
     counts = {}
     for d in launches:
+        if d["kind"] not in KINDS:
+            continue
         key = json.dumps(d, sort_keys=True)
         counts[key] = counts.get(key, 0) + 1
     del tr
