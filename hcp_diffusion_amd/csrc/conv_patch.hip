@@ -247,7 +247,6 @@ HCP_KERNEL(768) conv_patch_kernel(GemmParams p) {
         const hcp_bf16* pa = patch + (cc % 3) * PATCH_ELEMS + dy * W2 * BK;
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx) {
-            constexpr int unused = 0; (void)unused;
             const int dx = MODE == 1 ? kx : 2 - kx;
             const hcp_bf16* sp = ring + st * B_ELEMS;
             hcp_bf16x8 fa[TM], fb[TN];

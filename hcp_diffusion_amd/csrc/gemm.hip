@@ -13,8 +13,8 @@
 //   FAST variants (channel count a multiple of 64, no upsample / strided dgrad) hoist all
 //   per-row address math out of the K loop: one base offset + a 9-bit tap-validity mask per row,
 //   a wave-uniform (tap, channel) cursor advanced per K tile.
-// * 64*WGM*WGN threads, BK=64, LDS double buffer (row stride 72 bf16 = conflict-free
-//   ds_read_b128), register-staged prefetch of the next K tile, one barrier per K tile.
+// * 64*WGM*WGN threads (+ loader waves where a variant has them), BK=64.  K tiles travel global -> LDS by LDS-DMA into an unpadded,
+//   XOR-swizzled [rows][64] image (see gemm_glds_kernel), one or more barriers per K tile depending on the loop.
 //   MFMA is issued with swapped operands so each lane owns 4 consecutive N of one row:
 //   8-byte bf16x4 stores and float4 bias loads in the epilogue.
 // * Tile shapes are chosen per problem so the grid fills 256 CUs: BN=160 divides every
@@ -28,7 +28,6 @@ extern "C" int hcp_geglu_fwd(const void* h, void* y, long M, int F, hipStream_t 
 namespace {
 
 using namespace hcp_gemm;
-
 
 HCP_DEVICE void epilogue_store(const GemmParams& p, int m, int n, hcp_f32x4 v) {
     if (p.geglu_hg) { epilogue_geglu_bwd(p, m, n, v); return; }
@@ -46,15 +45,14 @@ HCP_DEVICE void epilogue_store(const GemmParams& p, int m, int n, hcp_f32x4 v) {
 }
 
 // MODE: 0 plain A, 1 conv forward gather, 2 conv data-gradient gather.  FAST: hoisted im2col addressing.
-// (The first, register-staged main loop — global -> VGPR -> ds_write_b128 — was removed after the LDS-DMA loop replaced it.)
 
 // 16 zero bytes in device memory: the source of every masked lane of an LDS-DMA load (out-of-range rows / columns,
 // the zero padding of the convolution, K tails).
 HCP_DEVICE_GLOBAL __attribute__((aligned(16))) unsigned char g_zero_page[16];
 
 // ---------------------------------------------------------------------------------------------------------------
-// LDS-DMA main loop.  Same tiling, fragment mapping, epilogues and fused-LoRA tail as gemm_kernel, but the K tiles
-// travel global -> LDS with global_load_lds_dwordx4 (no VGPR staging, no ds_write: the register-staged loop is bound
+// LDS-DMA main loop (the first one; gemm_v2_kernel below is what the dispatcher takes wherever its requirements hold).  The K tiles
+// travel global -> LDS with global_load_lds_dwordx4 (no VGPR staging, no ds_write: a register-staged loop is bound
 // by the ~79 B/clk ds_write_b128 port, not by MFMA).  DMA destinations are lane-linear, so the LDS image is unpadded
 // [rows][64] and bank conflicts are removed by an XOR swizzle applied to the SOURCE chunk index and to the reads:
 // position (r, c) holds global chunk c ^ ((r >> 1) & 7), which makes the 16-lane ds_read_b128 groups of this
@@ -363,7 +361,7 @@ HCP_KERNEL(64 * WGM * WGN) gemm_glds_kernel(GemmParams p) {
 //     re-pointed at each K tile (a few SALU ops), every lane's byte offset is LOOP-INVARIANT, and a masked row / conv tap is
 //     an out-of-range offset that the hardware turns into zeros — no zero page, no exec-mask branches, no 64-bit VALU math;
 //   * LDS fragment addresses are two precomputed VGPRs per operand (the XOR swizzle does not depend on the 16-row block);
-//   * the rank-32 K-extension tile and the epilogue are outside the loop; no ablation hooks.
+//   * the rank-32 K-extension tile and the epilogue are outside the loop; ablation hooks in the tools build only.
 // Requirements (else the dispatcher keeps the kernel above): K % 64 == 0; conv gathers in their FAST form.
 // NLD > 0: wave specialisation.  NLD extra "loader" waves issue ALL of the tile's LDS-DMA instructions; the WGM x WGN compute waves
 // only read fragments and issue MFMAs.  An LDS-DMA instruction costs its issuing wave ~100+ cycles of in-order issue time (the
@@ -880,12 +878,11 @@ HCP_TUNABLE(int, g_force_cfg, -1);   // tools/tune: force a tile configuration (
 inline int forced_id(int v) { return v >= 1024 ? (v - 1024) % 64 : v % 16; }
 inline int forced_split(int v) { const int s = v >= 1024 ? (v - 1024) / 64 : v / 16; return s > 0 ? s : 1; }
 HCP_TUNABLE(int, g_dbg_ablate, 0);   // tools only, see GemmParams::dbg
-HCP_TUNABLE(int, g_use_glds, 1);     // 1: LDS-DMA main loop (default), 0: register-staged main loop (kept for A/B measurements)
-HCP_TUNABLE(int, g_use_v2, 1);       // 1: buffer-addressed v2 main loop where its requirements hold (default), 0: gemm_glds_kernel everywhere
+HCP_TUNABLE(int, g_use_v2, 1);       // 1: the buffer-addressed main loops where their requirements hold (default), 0: gemm_glds_kernel everywhere
 
 HCP_TUNABLE(int, g_conv_patch, 1);   // tools: 0 = the ping-pong kernel for every convolution, 1 = the rule in try_pp, 2 = conv_patch.hip wherever eligible
 HCP_TUNABLE(int, g_epi_tile, -1);    // tools: -1 = the rule below, 0 = lane-layout epilogue everywhere, 1 = tile epilogue wherever it is possible
-HCP_TUNABLE(int, g_force_loaders, -1);   // tools: -1 = as dispatched, 0 = no loader waves, 1 / 3 / 4 = loader-wave variant with a 2 / 3 / 4 tile ring
+HCP_TUNABLE(int, g_force_loaders, -1);   // tools: -1 = as dispatched, else the value of GemmParams::loaders (gemm_params.h)
 
 // Tile epilogue (gemm_params.h: epi_tile_store) for this launch?  Needs an unsplit bf16 output in 16-byte pieces.  The rule, from
 // tools/lab/epilogue_ab.py on rotating operand sets (profiles/r6_ab_tile_epilogue.txt): it wins where the epilogue READS — a plain GEMM
@@ -901,24 +898,39 @@ bool want_epi_tile(const GemmParams& p, int mode) {
     return mode == 0 && p.residual != nullptr;
 }
 
+// Behind a main-loop launch (`name`): a split-K launch gets the launch that sums its slabs and applies the epilogue; then the status.
+int launch_splitk_reduce(const GemmParams& p, hipStream_t stream, const char* name = "splitk_reduce_kernel") {
+    if (p.nsplit > 1) {
+        const long nv = (long)p.M * (p.N / 4);
+        int g = (int)((nv + 255) / 256); if (g > 2048) g = 2048;
+        HCP_LAUNCH(splitk_reduce_kernel, dim3(g), dim3(256), 0, stream, p);
+    }
+    HCP_LAUNCH_CHECK(name);
+}
+// Can the buffer-addressed loops (gemm_v2_kernel, gemm_pp.hip, conv_patch.hip) take this problem?  (conv gathers: FAST form only, the caller's business)
+bool buffer_loops_take(const GemmParams& p) {
+    return g_use_v2 && !(g_dbg_ablate & 7) && p.K % BK == 0 && (p.K2 == 0 || p.K2 == 32) &&
+           (size_t)p.M * p.lda * 2 < (1ul << 31) && (size_t)p.N * p.ldb * 2 < (1ul << 31);
+}
+// GEGLU-forward epilogue (GemmParams::geglu_out): a tile bn columns wide, its waves wgn across, pairs the h and g halves, or geglu_out is cleared.
+void pair_geglu_or_clear(GemmParams& p, int mode, int bn, int wgn) {
+    if (p.geglu_out && mode == 0 && wgn % 2 == 0 && p.nsplit == 1 && (p.N / 2) % (bn / 2) == 0) p.geglu_fused = 1;
+    else p.geglu_out = nullptr;
+}
 template <int BM, int BN, int WGM, int WGN, int MODE, bool FAST, bool LORA = false, int NSTAGE = 2, int NLD = 0>
 int launch_cfg(GemmParams& p, hipStream_t stream) {
     p.tiles_m = hcp_cdiv(p.M, BM);
     const int tiles_n = hcp_cdiv(p.N, BN);
     p.dbg = g_dbg_ablate;
+    constexpr size_t tail = (size_t)(2 * BM + BN) * 40 * sizeof(hcp_bf16);   // fused-LoRA tail images: T_hi, E, T_lo
     if constexpr (NSTAGE == 2 && (MODE == 0 || FAST)) {
-        if (g_use_v2 && g_use_glds && !(p.dbg & 7) && p.K % BK == 0 && (p.K2 == 0 || p.K2 == 32) &&
-            (size_t)p.M * p.lda * 2 < (1ul << 31) && (size_t)p.N * p.ldb * 2 < (1ul << 31)) {
+        if (buffer_loops_take(p)) {
             constexpr size_t stage = (size_t)(BM + BN + (LORA ? 32 : 0)) * BK * sizeof(hcp_bf16);
             constexpr size_t eimg = (LORA && NLD > 0) ? (size_t)BN * 32 * sizeof(hcp_bf16) : 0;   // loader variant: the E rows, behind the ring
-            if (p.geglu_out) {                               // GEGLU-forward epilogue: this tile must pair h and g columns (gemm_params.h)
-                if (MODE == 0 && WGN % 2 == 0 && p.nsplit == 1 && (p.N / 2) % (BN / 2) == 0) p.geglu_fused = 1;
-                else p.geglu_out = nullptr;
-            }
+            pair_geglu_or_clear(p, MODE, BN, WGN);          // GEGLU-forward epilogue: this tile must pair h and g columns (gemm_params.h)
             constexpr size_t tile_bytes = (size_t)BM * epi_tile_ld(BN) * sizeof(float);
             p.epi_tile = want_epi_tile(p, MODE) && tile_bytes <= 160 * 1024 - eimg ? 1 : 0;
             size_t smem = 2 * stage;
-            const size_t tail = (size_t)(2 * BM + BN) * 40 * sizeof(hcp_bf16);   // fused-LoRA tail images: T_hi, E, T_lo
             if (LORA && smem < tail) smem = tail;
             if (p.epi_tile && smem < tile_bytes) smem = tile_bytes;
             [[maybe_unused]] const dim3 grid(p.tiles_m * tiles_n, p.nsplit);
@@ -937,29 +949,18 @@ int launch_cfg(GemmParams& p, hipStream_t stream) {
             } else {
                 HCP_LAUNCH((gemm_v2_kernel<BM, BN, WGM, WGN, MODE, LORA>), dim3(p.tiles_m * tiles_n, p.nsplit), dim3(64 * WGM * WGN), smem, stream, p);
             }
-            if (p.nsplit > 1) {
-                long nv = (long)p.M * (p.N / 4);
-                int g = (int)((nv + 255) / 256); if (g > 2048) g = 2048;
-                HCP_LAUNCH(splitk_reduce_kernel, dim3(g), dim3(256), 0, stream, p);
-            }
-            HCP_LAUNCH_CHECK("gemm_v2_kernel");
+            return launch_splitk_reduce(p, stream, "gemm_v2_kernel");
         }
     }
     {
         p.epi_tile = 0;
         p.geglu_out = nullptr;                               // (the first LDS-DMA loop has no pairing epilogue: the entry point runs hcp_geglu_fwd behind it)
         size_t smem = (size_t)NSTAGE * (BM + BN + (LORA ? 32 : 0)) * BK * sizeof(hcp_bf16);
-        const size_t tail = (size_t)(2 * BM + BN) * 40 * sizeof(hcp_bf16);  // fused-LoRA tail images: T_hi, E, T_lo
         if (LORA && smem < tail) smem = tail;
         HCP_LAUNCH((gemm_glds_kernel<BM, BN, WGM, WGN, MODE, FAST, LORA, NSTAGE>), dim3(p.tiles_m * tiles_n, p.nsplit),
                    dim3(64 * WGM * WGN), smem, stream, p);
     }
-    if (p.nsplit > 1) {
-        long nv = (long)p.M * (p.N / 4);
-        int g = (int)((nv + 255) / 256); if (g > 2048) g = 2048;
-        HCP_LAUNCH(splitk_reduce_kernel, dim3(g), dim3(256), 0, stream, p);
-    }
-    HCP_LAUNCH_CHECK("gemm_kernel");
+    return launch_splitk_reduce(p, stream, "gemm_kernel");
 }
 
 struct TileCfg { int bm, bn; };
@@ -972,17 +973,13 @@ constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
 // p.loaders >= 8: the ping-pong main loop (gemm_pp.hip) with an LDS ring of p.loaders - 8 tiles, where it is instantiated for
 // this tile shape and its requirements hold (the v2 ones: K % 64 == 0, FAST conv gathers, 32-bit offsets).  -2 = not taken.
 int try_pp(int id, int mode, bool fast_or_plain, bool lora, GemmParams& p, hipStream_t stream) {
-    if (p.loaders < 8 || !fast_or_plain || !g_use_v2 || (g_dbg_ablate & 7)) return -2;
-    if (p.K % BK != 0 || !(p.K2 == 0 || p.K2 == 32) || (size_t)p.M * p.lda * 2 >= (1ul << 31) || (size_t)p.N * p.ldb * 2 >= (1ul << 31)) return -2;
+    if (p.loaders < 8 || !fast_or_plain || !buffer_loops_take(p)) return -2;
     const int bm = kCfgs[id].bm, bn = kCfgs[id].bn;
     p.tiles_m = hcp_cdiv(p.M, bm);
     p.dbg = g_dbg_ablate;
     p.epi_tile = want_epi_tile(p, mode) ? 1 : 0;            // (gemm_pp_launch clears it where the tile does not fit)
-    hcp_bf16* const gout = p.geglu_out;                     // GEGLU-forward epilogue: see launch_cfg
-    if (gout) {
-        if (mode == 0 && p.nsplit == 1 && (p.N / 2) % (bn / 2) == 0) p.geglu_fused = 1;
-        else p.geglu_out = nullptr;
-    }
+    hcp_bf16* const gout = p.geglu_out;                     // GEGLU-forward epilogue: see launch_cfg (two waves across N)
+    pair_geglu_or_clear(p, mode, bn, 2);
     int r = -2;
     // LDS-resident input patch (conv_patch.hip) where it wins (profiles/r6_ab_conv_patch.txt): data gradients (-4 ... -7 %) and split-K
     // launches (its chunk-aligned split needs fewer slabs: SDXL C640 @64x64 -25 %); unsplit forward convolutions are 1-10 % faster on the
@@ -992,10 +989,7 @@ int try_pp(int id, int mode, bool fast_or_plain, bool lora, GemmParams& p, hipSt
     if (r == -2) r = gemm_pp_launch(p, bm, bn, mode, lora, p.loaders - 8, stream);
     if (r == -2) { p.geglu_out = gout; p.geglu_fused = 0; }     // not instantiated for this tile: the caller's own kernels decide again
     if (r != 0 || p.nsplit <= 1) return r;
-    long nv = (long)p.M * (p.N / 4);
-    int g = (int)((nv + 255) / 256); if (g > 2048) g = 2048;
-    HCP_LAUNCH(splitk_reduce_kernel, dim3(g), dim3(256), 0, stream, p);
-    HCP_LAUNCH_CHECK("splitk_reduce_kernel");
+    return launch_splitk_reduce(p, stream);
 }
 
 template <int MODE, bool FAST>
@@ -1177,12 +1171,11 @@ HCP_API int hcp_debug_gemm_table_stats(long* hits, long* misses) {
 }
 // TOOLS ONLY (tools/tune_gemm.py): cfg = tile id + 16 * nsplit (ids 0-15), or 1024 + tile id + 64 * nsplit (any id); -1 restores the heuristic.
 HCP_API int hcp_debug_set_gemm_config(int cfg) { g_force_cfg = cfg; return 0; }
-// TOOLS ONLY: 1 = default (v2 main loop where its requirements hold), 0 / 2 = the first LDS-DMA loop (gemm_glds_kernel) everywhere.
-HCP_API int hcp_debug_set_gemm_glds(int on) { g_use_glds = 1; g_use_v2 = on == 1; return 0; }
-// TOOLS ONLY: ablation (results are wrong when != 0).  First LDS-DMA loop: 1 no DMA after tile 0, 2 no MFMA, 4 no LDS reads;
-// v2 loop (tools build only): 8 no DMA after the ring prologue, 16 no MFMA, 32 no LDS fragment reads, 64 no output stores.
+// TOOLS ONLY: 1 = default (v2 main loop where eligible), 0 / 2 = the first LDS-DMA loop (gemm_glds_kernel) everywhere.
+HCP_API int hcp_debug_set_gemm_glds(int on) { g_use_v2 = on == 1; return 0; }
+// TOOLS ONLY: ablation (results are wrong when != 0); the flags are listed at GemmParams::dbg (gemm_params.h).
 HCP_API int hcp_debug_set_gemm_ablation(int flags) { g_dbg_ablate = flags; return 0; }
-// TOOLS ONLY: -1 = as the dispatch table says, 0 = never, 1 = the loader-wave variant wherever one is instantiated (tile ids 12-15).
+// TOOLS ONLY: -1 = as the dispatch table says, else the value of GemmParams::loaders (gemm_params.h) for every launch.
 HCP_API int hcp_debug_set_gemm_loaders(int mode) { g_force_loaders = mode; return 0; }
 // TOOLS ONLY: -1 = the rule (want_epi_tile), 0 = lane-layout epilogue everywhere, 1 = tile epilogue (16-byte row pieces through LDS) wherever possible.
 HCP_API int hcp_debug_set_gemm_epilogue(int mode) { g_epi_tile = mode; return 0; }

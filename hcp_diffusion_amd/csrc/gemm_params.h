@@ -1,4 +1,5 @@
-// gemm_params.h — the launch descriptor shared by the GEMM / implicit-conv translation units (gemm.hip, gemm_pp.hip).
+// gemm_params.h — what the GEMM / implicit-conv translation units (gemm.hip, gemm_pp.hip, conv_patch.hip) share: the launch descriptor
+// (GemmParams) and the epilogue pieces that exist once (hi / lo store, tile epilogue, GEGLU tiles and pairing).
 #pragma once
 #include "hcp_common.h"
 
@@ -53,8 +54,15 @@ struct GemmParams {
     // "tile epilogue" (round 6): the finished fp32 values go through an LDS tile and leave in 16-byte pieces of full output rows (residual
     // read the same way) instead of 8-byte pieces in the MFMA lane layout — see epi_tile_store below; set by the dispatcher.
     int epi_tile;
-    int loaders;                    // 1: launch the loader-wave variant of the v2 kernel where one is instantiated (dispatch table / tools)
-    int dbg;                        // tools/ablate_gemm.py: 1 = skip the DMA after the first tile, 2 = skip the MFMAs, 4 = skip LDS reads + MFMAs
+    // Main loop (table column `loaders`, hcp_debug_set_gemm_loaders): 0 = every wave loads and computes; 1 / 3 / 4 = loader-wave variant of
+    // gemm_v2_kernel where one is instantiated (tile ids 13-16), LDS ring of 2 / 3 / 4 K tiles (lowered to what fits 160 KB); 8 + ring =
+    // the ping-pong loop (gemm_pp.hip, or conv_patch.hip for the convolutions try_pp gives it), ring = 2 .. 4 K tiles.
+    int loaders;
+    // Ablation flags (hcp_debug_set_gemm_ablation; wrong results when != 0; bits 1 - 4 in every build, the others in the tools build).
+    // gemm_glds_kernel (any of the three keeps the launch there): 1 no DMA after tile 0, 2 no MFMA, 4 no LDS reads and no MFMA; gemm_v2_kernel:
+    // 8 no DMA after the ring prologue (loader waves), 16 no MFMA, 32 no LDS fragment reads, 64 no output stores; gemm_pp_kernel: 0x100 / 0x200
+    // loaders skip the A / B rows, 0x400 reads only, 0x800 barriers only, 0x1000 no raised MFMA priority, 0x2000 loader waves at priority 3.
+    int dbg;
     ConvDesc cv;
 };
 

@@ -354,12 +354,11 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
             if (p.dbg & 0x800) { hcp_barrier_only(); hcp_barrier_only(); continue; }     // ablation: barriers only
 #endif
             hcp_bf16x8 fa[TM], fb[TN], fl;
-            constexpr int x = 0;
 #pragma unroll
-            for (int i = 0; i < TM; ++i) fa[i] = *(const hcp_bf16x8*)(sp + (a_rd0 ^ x) + i * 16 * BK);
+            for (int i = 0; i < TM; ++i) fa[i] = *(const hcp_bf16x8*)(sp + a_rd0 + i * 16 * BK);
 #pragma unroll
-            for (int j = 0; j < TN; ++j) fb[j] = *(const hcp_bf16x8*)(sp + (b_rd0 ^ x) + j * 16 * BK);
-            if (LORA) fl = *(const hcp_bf16x8*)(sp + (l_rd0 ^ x));
+            for (int j = 0; j < TN; ++j) fb[j] = *(const hcp_bf16x8*)(sp + b_rd0 + j * 16 * BK);
+            if (LORA) fl = *(const hcp_bf16x8*)(sp + l_rd0);
             hcp_barrier_only();                           // the other group's MFMA block ends here; this wave's fragments are on their way
 #if defined(HCP_TOOLS)
             if (p.dbg & 0x400) {                          // ablation: fragment reads only, no MFMAs
