@@ -31,6 +31,10 @@ _PROTOTYPES = {
     # X1, C1, X2, C2, B, Hs, Ws, Ho, Wo, mode, stride, upsample, Wp, Cout, D, ldd, bias, rowbias, rowbias_ld,
     # residual, ldr, out_f32, workspace, workspace_bytes, stream
     "hcp_conv3x3_bf16": (I, [P, I, P, I, I, I, I, I, I, I, I, I, I, P, I, P, I, P, P, I, P, I, I, P, P, P, c_size_t, P]),
+    # W, Wf, Wdf, Cout, Cin, stream
+    "hcp_conv_fold_pack": (I, [P, P, P, I, I, P]),
+    # X, B, Hs, Ws, Cin, Cout, mode, Wfold, D, bias, workspace, workspace_bytes, stream
+    "hcp_conv3x3_up_fold_bf16": (I, [P, I, I, I, I, I, I, P, P, P, P, c_size_t, P]),
     # Q, K, V, O, lse, B, H, Nq, Nk, D, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs, scale, stream
     "hcp_attention_fwd": (I, [P, P, P, P, P, I, I, I, I, I, L, I, L, I, L, I, L, I, F, P, L, I, P]),
     # Q, K, V, O, dO, lse, delta, dQ, dK, dV, B, H, Nq, Nk, D, strides..., scale, workspace, workspace_bytes, stream
@@ -120,6 +124,7 @@ _TOOLS_PROTOTYPES = {
     "hcp_debug_set_gemm_loaders": (I, [I]),
     "hcp_debug_set_gemm_epilogue": (I, [I]),
     "hcp_debug_set_conv_patch": (I, [I]),
+    "hcp_debug_set_conv_fold": (I, [I]),
     "hcp_debug_set_gn_target": (I, [I]),
     "hcp_debug_set_gemm_ablation": (I, [I]),
     "hcp_debug_set_attention_config": (I, [I]),
@@ -132,7 +137,7 @@ TOOLS_SYMBOLS = tuple(_TOOLS_PROTOTYPES)
 TOOLS_LIB_PATH = Path(__file__).resolve().parent / "libhcp_mi355x_tools.so"
 
 
-ABI_VERSION = 4          # include/hcp_mi355x.h HCP_ABI_VERSION: bumped whenever an exported signature or descriptor layout changes
+ABI_VERSION = 5          # include/hcp_mi355x.h HCP_ABI_VERSION: bumped whenever an exported signature or descriptor layout changes
 
 
 class HcpError(RuntimeError):

@@ -881,6 +881,7 @@ HCP_TUNABLE(int, g_dbg_ablate, 0);   // tools only, see GemmParams::dbg
 HCP_TUNABLE(int, g_use_v2, 1);       // 1: the buffer-addressed main loops where their requirements hold (default), 0: gemm_glds_kernel everywhere
 
 HCP_TUNABLE(int, g_conv_patch, 1);   // tools: 0 = the ping-pong kernel for every convolution, 1 = the rule in try_pp, 2 = conv_patch.hip wherever eligible
+HCP_TUNABLE(int, g_conv_fold, 1);    // tools: 0 = hcp_conv3x3_up_fold_bf16 declines (returns 1, the caller runs the unfolded kernels): the A/B switch of the folded upsampler convs
 HCP_TUNABLE(int, g_epi_tile, -1);    // tools: -1 = the rule below, 0 = lane-layout epilogue everywhere, 1 = tile epilogue wherever it is possible
 HCP_TUNABLE(int, g_force_loaders, -1);   // tools: -1 = as dispatched, else the value of GemmParams::loaders (gemm_params.h)
 
@@ -1159,9 +1160,47 @@ int launch_lora_dispatched(GemmParams& p, void* workspace, size_t workspace_byte
     return launch_lora_by_id(id, p, stream);
 }
 
+// Folded upsampler convs (gemm_params.h: ConvDesc::fold_c): ping-pong kernel only, 160-wide tiles (ids 3 = 128 x 160, 4 = 64 x 160).
+// Table key: mode 4 (forward, M = B Hs Ws, N = 4 Cout, K = 4 Cin) / 5 (data gradient, M = B Hs Ws, N = Cin, K = 16 Cout_pad) in a table of
+// its own (gemm_tuned_fold.inc), else the rule below: the small tile until 128 x 160 fills the 256 CUs, and (data gradient) split-K
+// until ~256 workgroups are in flight with at least 16 K tiles each.
+const TunedEntry kTunedFold[] = {
+    {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0},     // (keeps the array non-empty)
+#include "gemm_tuned_fold.inc"
+};
+int dispatch_fold(GemmParams& p, int mode, float* ws, size_t ws_bytes, hipStream_t stream) {
+    int id = (long)hcp_cdiv(p.M, 128) * hcp_cdiv(p.N, 160) >= 256 ? 3 : 4, nsplit = 1, ring = 4;
+    const int nk1 = p.K / BK;
+    if (mode == 5) {
+        const long tiles = (long)hcp_cdiv(p.M, kCfgs[id].bm) * hcp_cdiv(p.N, 160);
+        while (nsplit < 16 && tiles * nsplit < 256 && nk1 / (nsplit * 2) >= 16) nsplit *= 2;
+    }
+    for (const TunedEntry& e : kTunedFold)
+        if (e.mode == mode && e.M == p.M && e.N == p.N && e.K == p.K) { id = e.cfg; nsplit = e.split; ring = e.loaders - 8; break; }
+    if (g_force_cfg >= 0) { id = forced_id(g_force_cfg); nsplit = forced_split(g_force_cfg); }
+    if (g_force_loaders >= 8) ring = g_force_loaders - 8;
+    if (mode == 4 || (size_t)nsplit * p.M * p.N * sizeof(float) > ws_bytes) nsplit = 1;       // (the forward's row remap lives in the kernel's own epilogue)
+    HCP_REQUIRE(id >= 0 && id < kNumCfgs && kCfgs[id].bn == 160 && (kCfgs[id].bm == 128 || kCfgs[id].bm == 64), "hcp_conv3x3_up_fold_bf16: tile id %d has no folded kernel", id);
+    p.loaders = 8 + ring;
+    p.nsplit = nsplit;
+    p.kt_per_split = hcp_cdiv(nk1, nsplit);
+    p.nsplit = hcp_cdiv(nk1, p.kt_per_split);
+    p.slabs = ws;
+    p.tiles_m = hcp_cdiv(p.M, kCfgs[id].bm);
+    p.dbg = 0;
+    p.epi_tile = 0;
+    HCP_REQUIRE(buffer_loops_take(p), "hcp_conv3x3_up_fold_bf16: operands too large for 32-bit offsets");
+    const int r = gemm_pp_launch(p, kCfgs[id].bm, 160, mode, false, ring, stream);
+    HCP_REQUIRE(r != -2, "hcp_conv3x3_up_fold_bf16: no kernel for tile id %d", id);
+    if (r != 0 || p.nsplit <= 1) return r;
+    return launch_splitk_reduce(p, stream);
+}
+
 }  // namespace
 
 #if defined(HCP_TOOLS)
+// TOOLS ONLY: 1 = default, 0 = hcp_conv3x3_up_fold_bf16 launches nothing and returns 1 (the caller then runs the unfolded 3x3 kernels).
+HCP_API int hcp_debug_set_conv_fold(int on) { g_conv_fold = on; return 0; }
 // TOOLS ONLY: dispatch-table lookups since the last call (hits, misses); resets the counters.
 HCP_API int hcp_debug_gemm_table_stats(long* hits, long* misses) {
     if (hits) *hits = g_table_hits;
@@ -1243,6 +1282,36 @@ HCP_API int hcp_conv3x3_bf16(const void* X1, int C1, const void* X2, int C2, int
     const bool fast = (C1 % 64 == 0) && (C2 % 64 == 0) && !upsample && !(mode == 1 && stride == 2);
     if (mode == 0) return fast ? dispatch_gemm<1, true>(p, ws, wb, stream) : dispatch_gemm<1, false>(p, ws, wb, stream);
     return fast ? dispatch_gemm<2, true>(p, ws, wb, stream) : dispatch_gemm<2, false>(p, ws, wb, stream);
+}
+
+// A 3x3 / pad-1 convolution behind a nearest-2x upsample (diffusers Upsample2D) with FOLDED weights (hcp_conv_fold_pack): every 2x2 block
+// of the upsampled image is one source pixel, so the nine taps collapse to 2x2 per output parity — 4/9 of the multiply-adds of
+// hcp_conv3x3_bf16(upsample = 1) and of its data gradient.  Hs x Ws = the LOW resolution in both modes.
+// mode 0 = forward:       X [B,Hs,Ws,Cin],     Wfold [2][2][Cout][2][2][Cin] -> D [B,2Hs,2Ws,Cout] (+ bias)
+// mode 1 = data gradient: X = dY [B,2Hs,2Ws,Cout], Wfold [Cin][4][4][Cout_pad] -> D = dX [B,Hs,Ws,Cin]  (the nearest-2x adjoint included;
+//                         Cout_pad = Cout rounded up to a multiple of 64)
+// Cin % 64 == 0 and Cout % 160 == 0 (other shapes: the caller keeps hcp_conv3x3_bf16).  Returns 1, with nothing launched, only under the
+// tools switch hcp_debug_set_conv_fold(0).
+HCP_API int hcp_conv3x3_up_fold_bf16(const void* X, int Bn, int Hs, int Ws, int Cin, int Cout, int mode, const void* Wfold, void* D,
+                                     const float* bias, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    HCP_REQUIRE(X && Wfold && D, "hcp_conv3x3_up_fold_bf16: null operand");
+    HCP_REQUIRE(mode == 0 || (mode == 1 && !bias), "hcp_conv3x3_up_fold_bf16: mode is 0 (forward) or 1 (data gradient, no bias)");
+    HCP_REQUIRE(Bn > 0 && Hs > 0 && Ws > 0 && Cin > 0 && Cout > 0 && Cin % 64 == 0 && Cout % 160 == 0,
+                "hcp_conv3x3_up_fold_bf16: needs Cin %% 64 == 0 and Cout %% 160 == 0 (Cin %d, Cout %d)", Cin, Cout);
+    HCP_REQUIRE(Hs <= 512 && Ws <= 512 && Bn < 2048 && (long)Bn * Hs * Ws * 4 * (Cin > Cout ? Cin : Cout) * 2 < (1L << 31),
+                "hcp_conv3x3_up_fold_bf16: tensors too large for 32-bit offsets");
+    if (!g_conv_fold) return 1;
+    GemmParams p = {};
+    p.cv.C1 = mode == 0 ? Cin : Cout; p.cv.X1 = (const hcp_bf16*)X;
+    p.cv.Ho = Hs; p.cv.Wo = Ws; p.cv.stride = 1; p.cv.pad = 1;
+    p.cv.Hs = mode == 0 ? Hs : 2 * Hs; p.cv.Ws = mode == 0 ? Ws : 2 * Ws;
+    p.M = Bn * Hs * Ws;
+    if (mode == 0) { p.N = 4 * Cout; p.K = 4 * Cin; p.ldd = 2 * Cout; p.cv.fold_c = Cout; }
+    else { p.N = Cin; p.K = 16 * ((Cout + BK - 1) / BK * BK); p.ldd = Cin; }
+    p.B = (const hcp_bf16*)Wfold; p.ldb = p.K;
+    p.D = D; p.bias = bias; p.alpha = 1.0f; p.rows_per_group = Hs * Ws;
+    if (int e = check_common(p)) return e;
+    return dispatch_fold(p, mode == 0 ? 4 : 5, (float*)workspace, workspace ? workspace_bytes : 0, stream);
 }
 
 // FF-out input-gradient with the GEGLU backward in its epilogue:  dY_ff[M,F] = dY W (+ LoRA side path, as hcp_gemm_lora_bf16's

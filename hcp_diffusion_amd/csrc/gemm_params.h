@@ -13,6 +13,15 @@ struct ConvDesc {
     int stride;                   // 1 or 2
     int up;                       // 1: source is nearest-upsampled 2x before the conv (fwd only)
     int pad;                      // 1: taps -1..+1 (padding 1); 0: taps 0..+2 (F.pad(0,1,0,1) + padding 0: the VAE encoder's Downsample2D), fwd only
+    // Folded upsampler conv (gemm_pp.hip MODE 4 / 5, hcp_conv3x3_up_fold_bf16): behind a nearest-2x upsample every 2x2 block of the 3x3
+    // conv's input is one source pixel, so an output pixel of parity (py, px) reads a 2x2 neighbourhood of the LOW-resolution source.
+    // MODE 4 (forward): rows = source pixels (Hs x Ws = Ho x Wo), columns = (parity, cout): N = 4 fold_c, a workgroup's N tile lies
+    //   inside one parity q = 2 py + px; K = 4 C1, tap (ty, tx) reads source (y + ty - 1 + py, x + tx - 1 + px); B = [4 fold_c][2][2][C1];
+    //   row m of parity q is stored at D + (2 m - m % Ws) ldd + (py 2 Ws + px) fold_c, ldd = 2 fold_c (NHWC at twice the resolution).
+    // MODE 5 (data gradient): rows = low-resolution pixels (Ho x Wo), source = dY at Hs x Ws = 2 Ho x 2 Wo with C1 channels; a 4x4
+    //   stride-2 pad-1 gather, K = 16 Cp (Cp = C1 rounded up to whole 64-channel K tiles), tap (ay, ax) reads dY (2 y + ay - 1, 2 x + ax - 1);
+    //   B = [Cin][4][4][Cp], zero in the padding; plain M x N output.
+    int fold_c;
 };
 
 struct GemmParams {

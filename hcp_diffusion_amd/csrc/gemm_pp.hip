@@ -80,11 +80,18 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
         if (p.dbg & 0x2000) hcp_setprio<3>();             // A/B: loaders above the MFMA blocks in the issue arbitration
 #endif
         // loop-invariant per-lane byte offsets; HCP_BUF_OOB = this lane contributes zeros (masked row / conv tap)
-        const int Ctot = p.cv.C1 + p.cv.C2;
+        // (folded data gradient: the K axis runs over dY's channels padded to whole K tiles — the weight image is zero there, and the
+        //  lanes of a tap's last, partial tile that stand for channels past C1 read zeros: tail_oob below)
+        const int Ctot = MODE == 5 ? (p.cv.C1 + BK - 1) / BK * BK : p.cv.C1 + p.cv.C2;
         unsigned va[A_IT], vb[B_IT];                      // MODE 0: byte offset of the row; conv: pixel index of the row
-        unsigned a_msk[(A_IT + 2) / 3];                   // conv: word i/3, bit 9*(i%3) + tap = tap valid for row i
+        constexpr int TB = MODE == 5 ? 16 : 9;            // taps of the gather (9; the folded forward's 4 fit too; folded data gradient: 16)
+        constexpr int RPW = 32 / TB;                      // rows whose tap masks share a 32-bit word
+        constexpr int NMW = (A_IT + RPW - 1) / RPW;
+        unsigned a_msk[NMW];                              // conv: word i/RPW, bit TB*(i%RPW) + tap = tap valid for row i
+        const int fold_q = MODE == 4 ? n0 / p.cv.fold_c : 0;      // folded forward: this N tile's output parity (py, px)
+        const int fold_py = fold_q >> 1, fold_px = fold_q & 1;
 #pragma unroll
-        for (int i = 0; i < (A_IT + 2) / 3; ++i) a_msk[i] = 0;
+        for (int i = 0; i < NMW; ++i) a_msk[i] = 0;
         const unsigned a_chunk = (unsigned)(((kc ^ ((lrow >> 1) & 7)) << 3) * 2);     // rows RPP apart share their swizzle term
 #pragma unroll
         for (int i = 0; i < B_IT; ++i) {
@@ -102,18 +109,32 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
                     const int hw = p.cv.Ho * p.cv.Wo;
                     const int b = m / hw; const int rem = m - b * hw;
                     const int py = rem / p.cv.Wo, px = rem - py * p.cv.Wo;
-                    const int s = MODE == 1 ? p.cv.stride : 1;
+                    const int s = MODE == 1 ? p.cv.stride : (MODE == 5 ? 2 : 1);
                     va[i] = (unsigned)((b * p.cv.Hs + py * s) * p.cv.Ws + px * s);
                     unsigned msk = 0;
+                    if (MODE == 4) {                      // 2x2 taps of this tile's parity around source pixel (py, px)
 #pragma unroll
-                    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                        for (int kx = 0; kx < 3; ++kx) {
-                            const int sy = MODE == 1 ? py * s + ky - p.cv.pad : py + 1 - ky;
-                            const int sx = MODE == 1 ? px * s + kx - p.cv.pad : px + 1 - kx;
-                            if (sy >= 0 && sy < p.cv.Hs && sx >= 0 && sx < p.cv.Ws) msk |= 1u << (ky * 3 + kx);
+                        for (int t = 0; t < 4; ++t) {
+                            const int sy = py + (t >> 1) - 1 + fold_py, sx = px + (t & 1) - 1 + fold_px;
+                            if (sy >= 0 && sy < p.cv.Hs && sx >= 0 && sx < p.cv.Ws) msk |= 1u << t;
                         }
-                    a_msk[i / 3] |= msk << (9 * (i % 3));
+                    } else if (MODE == 5) {               // 4x4 taps, stride 2, pad 1 over the high-resolution dY
+#pragma unroll
+                        for (int t = 0; t < 16; ++t) {
+                            const int sy = 2 * py + (t >> 2) - 1, sx = 2 * px + (t & 3) - 1;
+                            if (sy >= 0 && sy < p.cv.Hs && sx >= 0 && sx < p.cv.Ws) msk |= 1u << t;
+                        }
+                    } else {
+#pragma unroll
+                        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                            for (int kx = 0; kx < 3; ++kx) {
+                                const int sy = MODE == 1 ? py * s + ky - p.cv.pad : py + 1 - ky;
+                                const int sx = MODE == 1 ? px * s + kx - p.cv.pad : px + 1 - kx;
+                                if (sy >= 0 && sy < p.cv.Hs && sx >= 0 && sx < p.cv.Ws) msk |= 1u << (ky * 3 + kx);
+                            }
+                    }
+                    a_msk[i / RPW] |= msk << (TB * (i % RPW));
                 }
             }
         }
@@ -124,7 +145,7 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
         // VALU work of ANY wave on a SIMD holds up the MFMAs of the compute waves it shares the SIMD with (measured with conv_patch.hip,
         // LAB_NOTEBOOK round 6).  Now: the products are loop invariants (one set per source tensor of a concat) and an invalid tap ORs bit 31
         // into the offset (>= num_records = out of range): one v_bfe + one v_lshl_or per row.
-        unsigned vo1[MODE != 0 ? A_IT : 1], vo2[MODE != 0 ? A_IT : 1], a_nmsk[(A_IT + 2) / 3];
+        unsigned vo1[MODE != 0 ? A_IT : 1], vo2[MODE != 0 ? A_IT : 1], a_nmsk[NMW];
         if (MODE != 0) {
 #pragma unroll
             for (int i = 0; i < A_IT; ++i) {
@@ -133,8 +154,9 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
                 vo2[i] = live ? va[i] * (unsigned)(2 * p.cv.C2) + a_chunk : HCP_BUF_OOB;
             }
 #pragma unroll
-            for (int i = 0; i < (A_IT + 2) / 3; ++i) a_nmsk[i] = ~a_msk[i];
+            for (int i = 0; i < NMW; ++i) a_nmsk[i] = ~a_msk[i];
         }
+        const unsigned tail_oob = (MODE == 5 && ((kc ^ ((lrow >> 1) & 7)) << 3) >= (p.cv.C1 & (BK - 1))) ? HCP_BUF_OOB : 0u;
         const hcp_bf16* Ab = p.A + (size_t)kt_begin * BK;
         const hcp_bf16* Bb = p.B + (size_t)kt_begin * BK;
         const hcp_bf16* Lb = LORA ? p.L + (size_t)kt_begin * BK : nullptr;
@@ -169,22 +191,29 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
                             if (qa + i >= q0 && qa + i < q1) hcp_buf_glds16(ra, va[i], la + (wave * 8 + RPP * i) * BK);
                     } else {
                         const int ky = tap / 3, kx = tap - ky * 3;
-                        const int doff = MODE == 1 ? (ky - p.cv.pad) * p.cv.Ws + (kx - p.cv.pad) : (1 - ky) * p.cv.Ws + (1 - kx);
+                        const int doff = MODE == 4 ? ((tap >> 1) - 1 + fold_py) * p.cv.Ws + ((tap & 1) - 1 + fold_px)     // (loop-invariant per parity and tap)
+                                       : MODE == 5 ? ((tap >> 2) - 1) * p.cv.Ws + ((tap & 3) - 1)
+                                       : MODE == 1 ? (ky - p.cv.pad) * p.cv.Ws + (kx - p.cv.pad) : (1 - ky) * p.cv.Ws + (1 - kx);
                         const bool first = cb < p.cv.C1;
                         const hcp_bf16* base = first ? p.cv.X1 + (long)doff * p.cv.C1 + cb : p.cv.X2 + (long)doff * p.cv.C2 + (cb - p.cv.C1);
                         const hcp_rsrc ra = hcp_make_rsrc(base);
                         // (two copies of the loop under a wave-uniform branch: `first ? vo1[i] : vo2[i]` made hipcc keep both arrays in SCRATCH —
                         //  a scratch load per row inside the loop, whose vmcnt wait drains the DMA queue: +25 % on every convolution)
-                        if (first) {
+                        if (MODE == 5 && cb + BK > p.cv.C1) {        // (wave-uniform; never taken when C1 % 64 == 0)
 #pragma unroll
                             for (int i = 0; i < A_IT; ++i)
                                 if (qa + i >= q0 && qa + i < q1)
-                                    hcp_buf_glds16(ra, vo1[i] | (((a_nmsk[i / 3] >> (9 * (i % 3) + tap)) & 1u) << 31), la + (wave * 8 + RPP * i) * BK);
+                                    hcp_buf_glds16(ra, vo1[i] | tail_oob | (((a_nmsk[i / RPW] >> (TB * (i % RPW) + tap)) & 1u) << 31), la + (wave * 8 + RPP * i) * BK);
+                        } else if (first) {
+#pragma unroll
+                            for (int i = 0; i < A_IT; ++i)
+                                if (qa + i >= q0 && qa + i < q1)
+                                    hcp_buf_glds16(ra, vo1[i] | (((a_nmsk[i / RPW] >> (TB * (i % RPW) + tap)) & 1u) << 31), la + (wave * 8 + RPP * i) * BK);
                         } else {
 #pragma unroll
                             for (int i = 0; i < A_IT; ++i)
                                 if (qa + i >= q0 && qa + i < q1)
-                                    hcp_buf_glds16(ra, vo2[i] | (((a_nmsk[i / 3] >> (9 * (i % 3) + tap)) & 1u) << 31), la + (wave * 8 + RPP * i) * BK);
+                                    hcp_buf_glds16(ra, vo2[i] | (((a_nmsk[i / RPW] >> (TB * (i % RPW) + tap)) & 1u) << 31), la + (wave * 8 + RPP * i) * BK);
                         }
                     }
                 }
@@ -324,10 +353,11 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
                                                           // leaves ~2 us of round trip exposed (measured: conv C320 64x64 36.3 -> 38.2 us)
     hcp_f32x4 bias_v[TNF];
     hcp_bf16x4 res_v[TMF][TNF];
+    const int nc0 = MODE == 4 ? n0 % p.cv.fold_c : n0;    // folded forward: the tile's first column inside its parity (bias, output)
     auto load_bias = [&]() {                              // 640 bytes shared by every workgroup of the N tile: an L2 hit, requested late
-        const hcp_rsrc rbias = hcp_make_rsrc_n(p.bias, p.bias ? (unsigned)p.N * 4u : 0u);
+        const hcp_rsrc rbias = hcp_make_rsrc_n(p.bias, p.bias ? (unsigned)(MODE == 4 ? p.cv.fold_c : p.N) * 4u : 0u);
 #pragma unroll
-        for (int j = 0; j < TNF; ++j) bias_v[j] = hcp_buf_load16f(rbias, (unsigned)geglu_col(p, BN, n0 + fcol0 + j * 16 + 4 * fg) * 4u);
+        for (int j = 0; j < TNF; ++j) bias_v[j] = hcp_buf_load16f(rbias, (unsigned)geglu_col(p, BN, nc0 + fcol0 + j * 16 + 4 * fg) * 4u);
     };
     // Rows past M need no select: their offset is >= the resource's num_records (ldr >= N), so the hardware range check returns zeros —
     // and a `m < M ? offset : OOB` select here compiled to divergent branches with a WAW `s_waitcnt vmcnt(0)` between the loads: TMF
@@ -492,6 +522,27 @@ HCP_KERNEL(768) gemm_pp_kernel(GemmParams p) {
         }
     }
 
+    if constexpr (MODE == 4) {                              // folded forward: NHWC at twice the resolution (gemm_params.h: fold_c); bias only, unsplit
+        const int q = n0 / p.cv.fold_c;
+        const size_t qoff = (size_t)((q >> 1) * 2 * p.cv.Ws + (q & 1)) * p.cv.fold_c;
+#pragma unroll
+        for (int i = 0; i < TMF; ++i) {
+            const int m = m0 + frow0 + i * 16 + fr;
+            if (m >= p.M) continue;
+            hcp_bf16* const drow = (hcp_bf16*)p.D + (size_t)(2 * m - m % p.cv.Ws) * p.ldd + qoff;
+#pragma unroll
+            for (int j = 0; j < TNF; ++j) {
+                const int n = n0 + fcol0 + j * 16 + 4 * fg;
+                if (j >= nfin || n >= p.N) continue;
+                const hcp_f32x4 v = acc[i][j] * p.alpha + bias_v[j];
+                hcp_bf16x4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = (short)hcp_f2bf(v[e]);
+                *(hcp_bf16x4*)(drow + (nc0 + fcol0 + j * 16 + 4 * fg)) = o;
+            }
+        }
+        return;
+    }
     if (p.nsplit > 1) {
 #pragma unroll
         for (int i = 0; i < TMF; ++i) {
@@ -621,6 +672,11 @@ int launch_pp_mode(GemmParams& p, int mode, bool lora, int ring, hipStream_t str
     if (lora) return launch_pp<BM, BN, 0, true>(p, ring, stream);
     if (mode == 0) return launch_pp<BM, BN, 0, false>(p, ring, stream);
     if (mode == 1) return launch_pp<BM, BN, 1, false>(p, ring, stream);
+    if constexpr (BN == 160) {                              // the folded upsampler convs (gemm_params.h: fold_c): 160-wide tiles only
+        if (mode == 4) return launch_pp<BM, BN, 4, false>(p, ring, stream);
+        if (mode == 5) return launch_pp<BM, BN, 5, false>(p, ring, stream);
+    }
+    if (mode != 2) return -2;
     return launch_pp<BM, BN, 2, false>(p, ring, stream);
 }
 

@@ -57,7 +57,57 @@ HCP_KERNEL(256) pack_weights_kernel(const PackPiece* pieces, int count) {
     }
 }
 
+// Folded images of an upsampler's 3x3 weight (include/hcp_mi355x.h: hcp_conv_fold_pack).  Behind a nearest-2x upsample the kernel rows
+// that read the same source row add up: output parity 0 reads source row y - 1 through ky = 0 and row y through ky = 1, 2; parity 1 reads
+// row y through ky = 0, 1 and row y + 1 through ky = 2 (columns alike).  The taps are summed in fp32 in ascending (ky, kx) order and rounded
+// to bf16 ONCE.  One thread per output element, a one-off per frozen weight (the transposed image reads W with stride 9 Cin: not tuned).
+//   forward image  Wf  [py][px][Cout][ty][tx][Cin]: ky in {0} | {1, 2} (py = 0), {0, 1} | {2} (py = 1) for ty = 0 | 1
+//   data gradient  Wdf [Cin][ay][ax][Cout_pad]:     ky in {2}, {1, 2}, {0, 1}, {0} for ay = 0 .. 3 (dY row 2 y + ay - 1); Cout_pad = Cout
+//                  rounded up to whole 64-channel K tiles, zeros in the padding
+HCP_DEVICE float fold_sum(const float* w, int klo_y, int khi_y, int klo_x, int khi_x, int cin) {
+    float sacc = 0.f;
+    bool first = true;
+    for (int ky = klo_y; ky <= khi_y; ++ky)
+        for (int kx = klo_x; kx <= khi_x; ++kx) {
+            const float v = w[(size_t)(ky * 3 + kx) * cin];
+            sacc = first ? v : sacc + v;
+            first = false;
+        }
+    return sacc;
+}
+HCP_KERNEL(256) conv_fold_pack_kernel(const float* W, hcp_bf16* Wf, hcp_bf16* Wdf, int Cout, int Cin) {
+    const long n = (long)16 * Cout * Cin;
+    const int Cp = (Cout + 63) / 64 * 64;
+    const long nd = (long)16 * Cp * Cin;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < n + nd; idx += (long)gridDim.x * 256) {
+        if (idx < n) {                                      // forward image: idx = ((((py 2 + px) Cout + co) 2 + ty) 2 + tx) Cin + ci
+            const int ci = (int)(idx % Cin); long r = idx / Cin;
+            const int tx = (int)(r & 1), ty = (int)((r >> 1) & 1); r >>= 2;
+            const int co = (int)(r % Cout), q = (int)(r / Cout), py = q >> 1, px = q & 1;
+            const int ylo = py == 0 ? (ty == 0 ? 0 : 1) : (ty == 0 ? 0 : 2), yhi = py == 0 ? (ty == 0 ? 0 : 2) : (ty == 0 ? 1 : 2);
+            const int xlo = px == 0 ? (tx == 0 ? 0 : 1) : (tx == 0 ? 0 : 2), xhi = px == 0 ? (tx == 0 ? 0 : 2) : (tx == 0 ? 1 : 2);
+            Wf[idx] = hcp_f2bf(fold_sum(W + (size_t)co * 9 * Cin + ci, ylo, yhi, xlo, xhi, Cin));
+        } else {                                            // data-gradient image: j = ((ci 4 + ay) 4 + ax) Cout_pad + co
+            const long j = idx - n;
+            const int co = (int)(j % Cp); long r = j / Cp;
+            if (co >= Cout) { Wdf[j] = 0; continue; }
+            const int ax = (int)(r & 3), ay = (int)((r >> 2) & 3); const int ci = (int)(r >> 4);
+            const int ylo = ay == 0 ? 2 : (ay == 1 ? 1 : 0), yhi = ay == 0 ? 2 : (ay == 1 ? 2 : (ay == 2 ? 1 : 0));
+            const int xlo = ax == 0 ? 2 : (ax == 1 ? 1 : 0), xhi = ax == 0 ? 2 : (ax == 1 ? 2 : (ax == 2 ? 1 : 0));
+            Wdf[j] = hcp_f2bf(fold_sum(W + (size_t)co * 9 * Cin + ci, ylo, yhi, xlo, xhi, Cin));
+        }
+    }
+}
+
 }  // namespace
+
+HCP_API int hcp_conv_fold_pack(const float* W, void* Wf, void* Wdf, int Cout, int Cin, hipStream_t stream) {
+    HCP_REQUIRE(W && Wf && Wdf && Cout > 0 && Cin > 0, "hcp_conv_fold_pack: bad arguments");
+    const long n = (long)16 * Cin * (Cout + (Cout + 63) / 64 * 64);
+    int g = (int)((n + 255) / 256); if (g > 8192) g = 8192;
+    HCP_LAUNCH(conv_fold_pack_kernel, dim3(g), dim3(256), 0, stream, W, (hcp_bf16*)Wf, (hcp_bf16*)Wdf, Cout, Cin);
+    HCP_LAUNCH_CHECK("conv_fold_pack");
+}
 
 HCP_API int hcp_pack_piece_bytes(void) { return (int)sizeof(PackPiece); }
 

@@ -224,10 +224,13 @@ def gemm_geglu_bwd(dy, wt, hg, *, l=None, e=None, want_t=True):
 
 
 def conv3x3(x1, wp, cout, *, x2=None, stride=1, upsample=False, mode=0, out_hw=None, bias=None, rowbias=None,
-            residual=None, out_f32=False, a2=None, b2=None, pad=1, out=None):
+            residual=None, out_f32=False, a2=None, b2=None, pad=1, out=None, fold=None):
     """3x3 convolution on NHWC bf16. mode 0: forward (wp = [cout][3][3][C1+C2]); mode 1: data gradient
     (x1 = dY [B,Hs,Ws,C1], wp = [cin][3][3][C1], out_hw = spatial dims of the forward input).  pad=0 (forward only): the VAE
-    encoder's asymmetric Downsample2D, F.pad(x, (0,1,0,1)) + padding 0.  out: optional contiguous [B,Ho,Wo,cout] output buffer."""
+    encoder's asymmetric Downsample2D, F.pad(x, (0,1,0,1)) + padding 0.  out: optional contiguous [B,Ho,Wo,cout] output buffer.
+    fold: the folded operand image of a nearest-2x upsampler's conv (conv_fold_pack) — mode 0 with upsample=True: the forward image, same
+    result shape; mode 1: the data-gradient image, x1 = the HIGH-resolution dY and the result is the LOW-resolution dX
+    [B,Hs/2,Ws/2,cout] (the nearest-2x adjoint included: no upsample2x_bwd behind it).  It is not part of the TRACE / LAUNCHES record."""
     assert x1.dtype == BF16 and x1.dim() == 4 and x1.is_contiguous()
     B, Hs, Ws, C1 = x1.shape
     C2 = 0
@@ -248,6 +251,12 @@ def conv3x3(x1, wp, cout, *, x2=None, stride=1, upsample=False, mode=0, out_hw=N
                 Cout=cout, stride=stride, upsample=1 if upsample else 0, pad=pad, Ho=Ho, Wo=Wo, ldd=cout, ldr=cout if residual is not None else 0,
                 bias=bias is not None, rowbias=rowbias is not None, rows_per_group=Ho * Wo if rowbias is not None else 0,
                 residual=residual is not None, out_f32=bool(out_f32))
+    if fold is not None:
+        assert C2 == 0 and stride == 1 and pad == 1 and rowbias is None and residual is None and a2 is None and not out_f32 and out is None
+        assert (mode == 0 and upsample) or (mode == 1 and bias is None and Hs % 2 == 0 and Ws % 2 == 0 and (Ho, Wo) == (Hs, Ws))
+        y = _conv3x3_fold(x1, fold, cout, mode, bias)
+        if y is not None:
+            return y            # (None: the tools switch hcp_debug_set_conv_fold(0) — the unfolded kernels below, then the nearest-2x adjoint)
     if out is None:
         out = torch.empty((B, Ho, Wo, cout), dtype=torch.float32 if out_f32 else BF16, device=x1.device)
     assert out.dtype == (torch.float32 if out_f32 else BF16) and out.is_contiguous() and tuple(out.shape) == (B, Ho, Wo, cout)
@@ -265,7 +274,48 @@ def conv3x3(x1, wp, cout, *, x2=None, stride=1, upsample=False, mode=0, out_hw=N
                                 cout, _p(out), cout, _p(bias), _p(rowbias), rowbias.stride(0) if rowbias is not None else 0,
                                 _p(residual), cout, 1 if out_f32 else 0, _p(a2), _p(b2), _p(ws), ws.numel(), _stream(x1)),
          "hcp_conv3x3_bf16")
-    return out
+    return upsample2x_bwd(out) if (fold is not None and mode == 1) else out
+
+
+def conv_fold_pack(w, wf, wdf):
+    """Folded operand images of a 3x3 convolution that follows a nearest-2x upsample, from its fp32 master w [Cout][3][3][Cin] (taps summed
+    in fp32, rounded once): wf [2][2][Cout][2][2][Cin] (forward: four 2x2 convolutions, one per output parity) and wdf [Cin][4][4][Cout_pad]
+    (data gradient: one 4x4 stride-2 pad-1 convolution over the high-resolution dY; Cout_pad = fold_cout_pad(Cout), zeros in the padding).
+    Both are written in place."""
+    cout, _, _, cin = w.shape
+    assert w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (cout, 3, 3, cin)
+    assert wf.dtype == BF16 and wf.is_contiguous() and tuple(wf.shape) == (2, 2, cout, 2, 2, cin)
+    assert wdf.dtype == BF16 and wdf.is_contiguous() and tuple(wdf.shape) == (cin, 4, 4, fold_cout_pad(cout))
+    _chk(lib().hcp_conv_fold_pack(_p(w), _p(wf), _p(wdf), cout, cin, _stream(w)), "hcp_conv_fold_pack")
+
+
+def fold_cout_pad(cout):
+    """Channels per tap of the folded data-gradient image: dY's channels in whole 64-wide K tiles."""
+    return (cout + 63) // 64 * 64
+
+
+def conv_fold_eligible(cin, cout):
+    """Shapes the folded upsampler kernels take: whole 64-channel K tiles inside one tap, N tiles (160 wide) inside one parity."""
+    return cin % 64 == 0 and cout % 160 == 0
+
+
+def _conv3x3_fold(x, wfold, cout, mode, bias):
+    B, Hx, Wx, Cx = x.shape
+    if mode == 0:
+        Hs, Ws, cin, co = Hx, Wx, Cx, cout
+        assert wfold.dtype == BF16 and wfold.is_contiguous() and tuple(wfold.shape) == (2, 2, co, 2, 2, cin)
+        y = torch.empty((B, 2 * Hs, 2 * Ws, co), dtype=BF16, device=x.device)
+    else:
+        Hs, Ws, cin, co = Hx // 2, Wx // 2, cout, Cx
+        assert wfold.dtype == BF16 and wfold.is_contiguous() and tuple(wfold.shape) == (cin, 4, 4, fold_cout_pad(co))
+        y = torch.empty((B, Hs, Ws, cin), dtype=BF16, device=x.device)
+    assert conv_fold_eligible(cin, co)
+    ws = _workspace(x)
+    rc = lib().hcp_conv3x3_up_fold_bf16(_p(x), B, Hs, Ws, cin, co, mode, _p(wfold), _p(y), _p(bias), _p(ws), ws.numel(), _stream(x))
+    if rc == 1:
+        return None
+    _chk(rc, "hcp_conv3x3_up_fold_bf16")
+    return y
 
 
 def wgrad_linear(dy, x, dw):

@@ -110,6 +110,22 @@ class HipConv2d(nn.Conv2d):
             self._pk = pk
         return self._pk
 
+    def folded(self):
+        """(forward image, data-gradient image) of a FROZEN upsampler conv (kernels.conv_fold_pack): behind a nearest-2x upsample the 3x3
+        taps collapse to 2x2 per output parity (4/9 of the work).  Built on the first upsample=True call, kept on packed() and refreshed
+        in place when only the weight's version moved (captured graphs hold the addresses)."""
+        pk = self.packed()
+        if getattr(pk, "fold_key", None) != pk.key:
+            w = self.weight.detach().permute(0, 2, 3, 1)
+            if w.dtype != torch.float32 or not w.is_contiguous():
+                w = w.float().contiguous()
+            if getattr(pk, "wf", None) is None:
+                pk.wf = torch.empty((2, 2, pk.cout, 2, 2, pk.cin), dtype=BF16, device=w.device)
+                pk.wdf = torch.empty((pk.cin, 4, 4, ops.K.fold_cout_pad(pk.cout)), dtype=BF16, device=w.device)
+            ops.K.conv_fold_pack(w, pk.wf, pk.wdf)
+            pk.fold_key = pk.key
+        return pk.wf, pk.wdf
+
     def forward(self, x, residual=None, x2=None, rowbias=None, upsample=False):
         if self.kernel_size == (1, 1):
             assert x2 is None and rowbias is None and not upsample

@@ -368,7 +368,13 @@ class _Conv3x3Fn(torch.autograd.Function):
             y = K.conv3x3(x1, pk.w, pk.cout, x2=x2, stride=stride, upsample=upsample, bias=pk.bias, rowbias=rowbias, residual=residual,
                           a2=T, b2=lp.bu)
         else:
-            y = K.conv3x3(x1, pk.w, pk.cout, x2=x2, stride=stride, upsample=upsample, bias=pk.bias, rowbias=rowbias, residual=residual)
+            # a FROZEN upsampler conv (LoRA / ControlNet training, inference) runs folded: 2x2 taps per output parity, 4/9 of the MFMA work
+            # (layers.HipConv2d.folded); trained weights, LoRA-wrapped convs and other shapes keep the 3x3 gather
+            fold = (upsample and stride == 1 and x2 is None and rowbias is None and residual is None and not host.weight.requires_grad
+                    and K.conv_fold_eligible(pk.cin, pk.cout))
+            ctx.fold = fold
+            y = K.conv3x3(x1, pk.w, pk.cout, x2=x2, stride=stride, upsample=upsample, bias=pk.bias, rowbias=rowbias, residual=residual,
+                          fold=host.folded()[0] if fold else None)
         ctx.host, ctx.stride, ctx.upsample, ctx.lora = host, stride, upsample, lora
         ctx.in_shape = x1.shape
         ctx.c2 = x2.shape[-1] if x2 is not None else 0
@@ -402,7 +408,9 @@ class _Conv3x3Fn(torch.autograd.Function):
                 dl1 = K.conv3x3(U, lp.wdl[:C1], C1, mode=1, stride=ctx.stride, out_hw=hw)
             if ctx.c2 and ctx.needs_input_grad[1]:
                 dl2 = K.conv3x3(U, lp.wdl[C1:], ctx.c2, mode=1, stride=ctx.stride, out_hw=hw)
-        if ctx.needs_input_grad[0]:
+        if ctx.needs_input_grad[0] and getattr(ctx, "fold", False):
+            dx1 = K.conv3x3(dy, pk.wd[:C1], C1, mode=1, stride=ctx.stride, out_hw=hw, fold=ctx.host.folded()[1])   # low-resolution dX directly
+        elif ctx.needs_input_grad[0]:
             dx1 = K.conv3x3(dy, pk.wd[:C1], C1, mode=1, stride=ctx.stride, out_hw=hw, residual=dl1)
             if ctx.upsample:
                 dx1 = K.upsample2x_bwd(dx1)

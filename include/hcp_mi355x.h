@@ -30,8 +30,8 @@ int hcp_is_emulated(void); /* 0 for the product library */
  * (ldt on hcp_gemm_lora_bf16 / hcp_gemm_geglu_bwd_bf16, l_lo, ldu / ldt) are covered by the same bump.  3: round 6 — the (hi | lo)
  * residual stream: residual_lo / D_lo on hcp_gemm_bf16 / hcp_gemm_lora_bf16, x_lo / addend_lo / dx_lo on hcp_layernorm_fwd / _bwd; the
  * GEGLU-forward output gact on hcp_gemm_bf16 / hcp_gemm_lora_bf16.  4: prompt tuning — hcp_embedding_pt_fwd_bf16 /
- * hcp_embedding_pt_bwd_f32 (csrc/embedding.hip). */
-#define HCP_ABI_VERSION 4
+ * hcp_embedding_pt_bwd_f32 (csrc/embedding.hip).  5: folded upsampler convs — hcp_conv_fold_pack / hcp_conv3x3_up_fold_bf16. */
+#define HCP_ABI_VERSION 5
 int hcp_abi_version(void);
 /* Device self-check of the fp32 atomic path (no reference counterpart: the reference's sums are torch's).  workgroups x 256 threads add
  * small integers into line[16] and into bucket[i * stride], i < nb (both cleared here first); exact expected values:
@@ -86,6 +86,18 @@ int hcp_conv3x3_bf16(const void* X1, int C1, const void* X2, int C2, int B, int 
                      int stride, int upsample, int pad, const void* Wp, int Cout, void* D, int ldd, const float* bias,
                      const float* rowbias, int rowbias_ld, const void* residual, int ldr, int out_f32, const void* A2,
                      const void* B2, void* workspace, size_t workspace_bytes, hcpStream_t stream);
+/* The 3x3 / pad-1 convolution behind a nearest-2x upsample (diffusers Upsample2D = F.interpolate(x, 2.0, "nearest") + conv) with FOLDED
+ * weights: every 2x2 block of the upsampled image is one source pixel, so the nine taps collapse to 2x2 per output parity (4/9 of the
+ * multiply-adds).  hcp_conv_fold_pack builds both images from the fp32 master W [Cout][3][3][Cin] (taps summed in fp32, one rounding):
+ *   Wf  [py][px][Cout][2][2][Cin]: rows (ky) {0} | {1,2} for py = 0, {0,1} | {2} for py = 1; columns alike
+ *   Wdf [Cin][4][4][Cout_pad]: taps {2}, {1,2}, {0,1}, {0} per axis — one 4x4 stride-2 pad-1 convolution over the high-resolution dY;
+ *       Cout_pad = Cout rounded up to a multiple of 64, zeros in the padding
+ * hcp_conv3x3_up_fold_bf16 (Hs x Ws = the LOW resolution; Cin % 64 == 0, Cout % 160 == 0):
+ *   mode 0: X [B,Hs,Ws,Cin], Wfold = Wf -> D [B,2Hs,2Ws,Cout] (+ bias);  mode 1: X = dY [B,2Hs,2Ws,Cout], Wfold = Wdf -> D = dX [B,Hs,Ws,Cin].
+ * For frozen weights only (the images are built once); returns 1 without launching only under the tools switch hcp_debug_set_conv_fold(0). */
+int hcp_conv_fold_pack(const float* W, void* Wf, void* Wdf, int Cout, int Cin, hcpStream_t stream);
+int hcp_conv3x3_up_fold_bf16(const void* X, int B, int Hs, int Ws, int Cin, int Cout, int mode, const void* Wfold, void* D,
+                             const float* bias, void* workspace, size_t workspace_bytes, hcpStream_t stream);
 
 /* Fused attention, element (b,n,h,c) at base + b*bs + n*rs + h*D + c; lse[B,H,Nq] = logsumexp(scale*QK^T).
  * Replaces diffusers CrossAttention/AttnProcessor2_0 (SDPA) or xformers (reference train_ac.py:258-260). D in {40,64,80,160}. */
