@@ -88,7 +88,6 @@ def atomics_selfcheck(device, workgroups=2048, nb=4099, stride=37):
     return True
 
 
-TRACE = None        # tools/autotune.py: a list collects the (kind, shape...) key of every GEMM-family launch
 # tools/trace_gemm_launches.py / tests/test_gemm_launches.py: a list collects one plain dict per GEMM-family launch — sizes, strides and
 # epilogue flags, enough to rebuild the call at its real shape (tests/gemm_check.py); tools/trace_attention_launches.py /
 # tests/test_attention_launches.py: the same for attention_fwd / attention_bwd (tests/attn_check.py).  None (the default): nothing is recorded.
@@ -100,11 +99,30 @@ def _launch(kind, **d):
     LAUNCHES.append(d)
 
 
-def _lo_pair(residual, residual_lo, want_lo, M, N, dev):
-    """Checks of the (hi | lo) residual-stream arguments shared by gemm / gemm_lora; returns the lo output tensor (or None)."""
+def trace_key(d):
+    """The tuners' (kind, shape...) key of one LAUNCHES record (tools/autotune.py): the launches that go through the tile dispatch — GEMM,
+    fused-LoRA GEMM (the GEGLU-backward GEMM counts as whichever of the two it is) and implicit-GEMM conv; None for every other kind."""
+    kind = d["kind"]
+    if kind == "gemm_lora" or (kind == "gemm_geglu_bwd" and d["lora"]):
+        return ("lora", d["M"], d["N"], d["K"])
+    if kind in ("gemm", "gemm_geglu_bwd"):
+        return ("gemm", d["M"], d["N"], d["K"], 1 if d.get("K2") else 0)
+    if kind == "conv3x3":
+        return ("conv", d["mode"], d["B"], d["Hs"], d["Ws"], d["C1"], d["C2"], d["Cout"], d["stride"], d["upsample"], d["Ho"], d["Wo"], 1 if d["K2"] else 0)
+    return None
+
+
+def _epilogue_args(bias, residual, residual_lo, want_lo, want_gact, M, N, dev):
+    """Checks of the bias / residual / (hi | lo) residual-stream arguments shared by gemm / gemm_lora; returns the (lo, gact) output
+    tensors (None where not asked for)."""
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.numel() == N and bias.is_contiguous()
+    if residual is not None:
+        _bf16_2d(residual, "residual"); assert residual.shape == (M, N)
     if residual_lo is not None:
         assert residual is not None and residual_lo.dtype == BF16 and residual_lo.shape == (M, N) and residual_lo.stride() == residual.stride()
-    return torch.empty((M, N), dtype=BF16, device=dev) if want_lo else None
+    return (torch.empty((M, N), dtype=BF16, device=dev) if want_lo else None,
+            torch.empty((M, N // 2), dtype=BF16, device=dev) if want_gact else None)
 
 
 def gemm(a, b, *, a2=None, b2=None, bias=None, rowbias=None, rows_per_group=1, residual=None, alpha=1.0,
@@ -121,8 +139,6 @@ def gemm(a, b, *, a2=None, b2=None, bias=None, rowbias=None, rows_per_group=1, r
         _bf16_2d(a2, "a2"); _bf16_2d(b2, "b2")
         K2 = a2.shape[1]
         assert a2.shape[0] == M and b2.shape == (N, K2)
-    if TRACE is not None:
-        TRACE.append(("gemm", M, N, K, 1 if K2 else 0))
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32 if out_f32 else BF16, device=a.device)
     assert out.stride(1) == 1
@@ -132,16 +148,11 @@ def gemm(a, b, *, a2=None, b2=None, bias=None, rowbias=None, rows_per_group=1, r
                 bias=bias is not None, rowbias=rowbias is not None, rows_per_group=rows_per_group if rowbias is not None else 0,
                 residual=residual is not None, residual_lo=residual_lo is not None, want_lo=bool(want_lo), gact=bool(want_gact),
                 alpha=float(alpha), out_f32=out.dtype == torch.float32)
-    if bias is not None:
-        assert bias.dtype == torch.float32 and bias.numel() == N and bias.is_contiguous()
     if rowbias is not None:
         assert rowbias.dtype == torch.float32 and rowbias.shape[1] == N and rowbias.stride(1) == 1
-    if residual is not None:
-        _bf16_2d(residual, "residual"); assert residual.shape == (M, N)
     ws = _workspace(a)
     assert not want_lo or (out.dtype == BF16 and out.is_contiguous())
-    out_lo = _lo_pair(residual, residual_lo, want_lo, M, N, a.device)
-    gact = torch.empty((M, N // 2), dtype=BF16, device=a.device) if want_gact else None
+    out_lo, gact = _epilogue_args(bias, residual, residual_lo, want_lo, want_gact, M, N, a.device)
     _chk(lib().hcp_gemm_bf16(_p(a), a.stride(0), _p(b), b.stride(0), _p(out), out.stride(0), M, N, K,
                              _p(a2), a2.stride(0) if a2 is not None else 0, _p(b2), b2.stride(0) if b2 is not None else 0,
                              K2, _p(bias), _p(rowbias), rowbias.stride(0) if rowbias is not None else 0, rows_per_group,
@@ -174,8 +185,6 @@ def gemm_lora(a, b, l, e, *, bias=None, residual=None, want_t=True, residual_lo=
     M, Kd = a.shape
     N = b.shape[0]
     assert b.shape[1] == Kd and l.shape == (32, Kd) and e.shape == (N, 32) and l.is_contiguous() and e.is_contiguous()
-    if TRACE is not None:
-        TRACE.append(("lora", M, N, Kd))
     out = torch.empty((M, N), dtype=BF16, device=a.device)
     ldt = 64 if T_SPLIT else 32
     if LAUNCHES is not None:
@@ -183,13 +192,8 @@ def gemm_lora(a, b, l, e, *, bias=None, residual=None, want_t=True, residual_lo=
                 ldr=residual.stride(0) if residual is not None else 0, bias=bias is not None, residual=residual is not None,
                 residual_lo=residual_lo is not None, want_lo=bool(want_lo), gact=bool(want_gact))
     t = torch.empty((M, ldt), dtype=BF16, device=a.device) if want_t else None
-    if bias is not None:
-        assert bias.dtype == torch.float32 and bias.numel() == N and bias.is_contiguous()
-    if residual is not None:
-        _bf16_2d(residual, "residual"); assert residual.shape == (M, N)
     ws = _workspace(a)
-    out_lo = _lo_pair(residual, residual_lo, want_lo, M, N, a.device)
-    gact = torch.empty((M, N // 2), dtype=BF16, device=a.device) if want_gact else None
+    out_lo, gact = _epilogue_args(bias, residual, residual_lo, want_lo, want_gact, M, N, a.device)
     _chk(lib().hcp_gemm_lora_bf16(_p(a), a.stride(0), _p(b), b.stride(0), _p(l), _p(e), _p(t), ldt, _p(out), N, M, N, Kd, _p(bias),
                                   _p(residual), residual.stride(0) if residual is not None else 0, _p(residual_lo), _p(out_lo), _p(gact),
                                   _p(ws), ws.numel(), _stream(a)),
@@ -206,8 +210,6 @@ def gemm_geglu_bwd(dy, wt, hg, *, l=None, e=None, want_t=True):
     M, C = dy.shape
     Fd = wt.shape[0]
     assert wt.shape[1] == C and hg.shape == (M, 2 * Fd) and hg.is_contiguous()
-    if TRACE is not None:
-        TRACE.append(("lora", M, Fd, C) if l is not None else ("gemm", M, Fd, C, 0))
     if LAUNCHES is not None:
         _launch("gemm_geglu_bwd", M=M, N=Fd, K=C, lda=dy.stride(0), ldb=wt.stride(0), ldd=2 * Fd, lora=l is not None,
                 ldt=(64 if T_SPLIT else 32) if l is not None else 0, want_t=bool(want_t) and l is not None)
@@ -230,7 +232,7 @@ def conv3x3(x1, wp, cout, *, x2=None, stride=1, upsample=False, mode=0, out_hw=N
     encoder's asymmetric Downsample2D, F.pad(x, (0,1,0,1)) + padding 0.  out: optional contiguous [B,Ho,Wo,cout] output buffer.
     fold: the folded operand image of a nearest-2x upsampler's conv (conv_fold_pack) — mode 0 with upsample=True: the forward image, same
     result shape; mode 1: the data-gradient image, x1 = the HIGH-resolution dY and the result is the LOW-resolution dX
-    [B,Hs/2,Ws/2,cout] (the nearest-2x adjoint included: no upsample2x_bwd behind it).  It is not part of the TRACE / LAUNCHES record."""
+    [B,Hs/2,Ws/2,cout] (the nearest-2x adjoint included: no upsample2x_bwd behind it).  The LAUNCHES record of such a call holds the unfolded 3x3 shape, not the folded operand."""
     assert x1.dtype == BF16 and x1.dim() == 4 and x1.is_contiguous()
     B, Hs, Ws, C1 = x1.shape
     C2 = 0
@@ -244,8 +246,6 @@ def conv3x3(x1, wp, cout, *, x2=None, stride=1, upsample=False, mode=0, out_hw=N
         Wo = (Ws * up + (2 if pad else 1) - 3) // stride + 1
     else:
         Ho, Wo = out_hw
-    if TRACE is not None:
-        TRACE.append(("conv", mode, B, Hs, Ws, C1, C2, cout, stride, 1 if upsample else 0, Ho, Wo, 1 if a2 is not None else 0))
     if LAUNCHES is not None:
         _launch("conv3x3", M=B * Ho * Wo, N=cout, K=9 * (C1 + C2), K2=32 if a2 is not None else 0, mode=mode, B=B, Hs=Hs, Ws=Ws, C1=C1, C2=C2,
                 Cout=cout, stride=stride, upsample=1 if upsample else 0, pad=pad, Ho=Ho, Wo=Wo, ldd=cout, ldr=cout if residual is not None else 0,

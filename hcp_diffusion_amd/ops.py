@@ -113,24 +113,78 @@ def grad_buffer(p, conv3x3=False):
     return g
 
 
+def _factors(lora):
+    """(W_down, W_up) of a layer's LoRA block: the inputs through which autograd sees the side path; (None, None) without one."""
+    return (lora.layer.W_down, lora.layer.W_up) if lora is not None else (None, None)
+
+
+def _lora_grads(wg, U, x2, T, dy2, members, ulo, tlo):
+    """dW_down / dW_up of every block in the (at most 32) rank slots of one U / T pair, through the wgrad context `wg`.
+    members: (blk, slot0) pairs (lora.members(): one block, or several sharing the slots — lora.MultiLora)."""
+    for blk, s0 in members:
+        gd, gu = blk.grad_views()
+        wg.add(U, x2, gd, T, dy2, gu, blk.rank, blk.alpha_f, s0, ulo, tlo)
+
+
+def _lora_grads_group(wg, U, x2, T, dy2, g, ulo, tlo):
+    """The same for a lora.FusedLoraGroup: every block owns its host's columns of dy2 and its alpha carries the host's out_scale."""
+    for blk, n0, s0, host, sc in zip(g.blocks, g.n_off, g.slot_off, g.hosts, g.out_scale):
+        if blk is not None:
+            gd, gu = blk.grad_views()
+            wg.add(U, x2, gd, T, dy2[:, n0:n0 + host.weight.shape[0]], gu, blk.rank, blk.alpha_f * sc, s0, ulo, tlo)
+
+
+def _lora_grads_wide(blk, s0, T2, dy2, U=None, x2=None):
+    """dW_up = alpha dY^T T of a block of any rank at column s0 of T2: 32 rank columns per launch of the skinny reduction kernel.  With
+    U and x2 (a Linear) dW_down = U^T x as well; the conv node forms its own with the im2col weight-gradient kernel.  Returns dW_down's view."""
+    gd, gu = blk.grad_views()
+    for j in range(0, blk.rank, 32):
+        pj = min(32, blk.rank - j)
+        if U is not None:
+            K.lora_wgrad(U[:, s0 + j:s0 + j + 32], x2, gd[j:j + pj], pj, 1.0, False)
+        K.lora_wgrad(T2[:, s0 + j:s0 + j + 32], dy2, gu, pj, blk.alpha_f, True, out_col0=j)
+    return gd
+
+
+def _host_grads(ctx, host, dy2, x2):
+    """Weight / bias gradients of a trainable Linear host, accumulated into its fp32 ``.grad``."""
+    if ctx.train_w:                                    # dW[N,K] += dY^T X (nn.Linear [N,K]; 1x1 conv [N,K,1,1] = same memory)
+        gw = grad_buffer(host.weight)
+        K.wgrad_linear(dy2, x2, gw.view(gw.shape[0], -1))
+    if ctx.train_b:
+        K.colsum(dy2, grad_buffer(host.bias))
+
+
 class _LinearFn(torch.autograd.Function):
     """y = x W^T (+ T (alpha Bu)^T) + bias (+ residual);  T = x Ad^T.   Reference arithmetic:
-    LoraPatchContainer.forward / LoraBlock.post_forward (lora_base_patch.py:20-35,68-74)."""
+    LoraPatchContainer.forward / LoraBlock.post_forward (lora_base_patch.py:20-35,68-74).
+    opt = (host, lora, out_f32, stream, kind):
+    stream: the residual is a (hi | lo) residual stream (residual, residual_lo — lo may be None where the stream starts) and the
+    result is the pair (y_hi, y_lo); their gradients come back as a pair too and pass to the residual inputs as they are.
+    kind "proj": the layer is diffusers' GEGLU projection — returns ((h | g), bf16(h * gelu(g))), the second formed in the GEMM epilogue
+    from the fp32 values (K.gemm(want_gact)); it carries no gradient of its own: the "ff" node, which consumes both, sends the whole
+    gradient back through (h | g).
+    kind "ff": y = FFout(h * gelu(g)) for x = (h | g), i.e. diffusers' FeedForward after its first projection (GEGLU + Dropout(0) + Linear,
+    cfgs/unet_struct.txt:27-33) as ONE node.  The GEMM input is `gact` (the "proj" node's second output) or the stand-alone GEGLU pass; the
+    backward runs the input-gradient GEMM with the GEGLU backward in its epilogue (hcp_gemm_geglu_bwd_bf16) — the [M, 4C] gradient of the
+    GEGLU output is never written or re-read.  Same arithmetic as _GegluFn + a plain node (the epilogue rounds dY_ff to bf16 before the two
+    products, as the two-kernel form does).  Rank <= 32 only (the assert in forward)."""
 
     @staticmethod
-    def forward(ctx, x, residual, w_down, w_up, host, lora, out_f32=False, hw=None, hb=None, residual_lo=None, stream=False, geglu=False):
-        """stream: the residual is a (hi | lo) residual stream (residual, residual_lo — lo may be None where the stream starts) and the
-        result is the pair (y_hi, y_lo); their gradients come back as a pair too and pass to the residual inputs as they are.
-        geglu: the layer is diffusers' GEGLU projection — returns ((h | g), bf16(h * gelu(g))), the second formed in the GEMM epilogue
-        from the fp32 values (K.gemm(want_gact)); it carries no gradient of its own: _GegluLinearFn, which consumes both, sends the
-        whole gradient back through (h | g)."""
+    def forward(ctx, x, residual, residual_lo, gact, w_down, w_up, hw, hb, opt):
+        host, lora, out_f32, stream, kind = opt
         shp = x.shape
         x2 = x.reshape(-1, shp[-1])
+        hg2 = None
+        if kind == "ff":
+            hg2, x2 = x2, (gact.reshape(-1, gact.shape[-1]) if gact is not None else K.geglu_fwd(x2))
         res2 = residual.reshape(-1, residual.shape[-1]) if residual is not None else None
         lo2 = residual_lo.reshape(-1, residual_lo.shape[-1]) if residual_lo is not None else None
         pk = host.packed()
+        geglu = kind == "proj"
         T = None
         if lora is not None and getattr(lora, "wide", False):      # rank > 32: skinny side GEMM + K-extension
+            assert hg2 is None, "the GEGLU + output-projection node takes LoRA blocks of rank <= 32 only"
             lp = lora.packed()
             T = K.gemm(x2, lp.ad)
             y = K.gemm(x2, pk.w, a2=T, b2=lp.bu, bias=pk.bias, residual=res2, residual_lo=lo2, want_lo=stream, want_gact=geglu)
@@ -142,88 +196,85 @@ class _LinearFn(torch.autograd.Function):
         ctx.host, ctx.lora = host, lora
         ctx.wg = current_wgrad()
         ctx.train_w, ctx.train_b = hw is not None, hb is not None
-        ctx.save_for_backward(x2 if (lora is not None or hw is not None) else None, T)
+        ctx.save_for_backward(x2 if (lora is not None or hw is not None) else None, T, hg2)
         ctx.xshape = shp
-        ctx.has_res = residual is not None
-        ctx.stream, ctx.has_lo = stream, residual_lo is not None
-        if geglu:
-            act = y[1].view(*shp[:-1], y[1].shape[-1])
-            ctx.mark_non_differentiable(act)
-            ctx.set_materialize_grads(False)           # (else autograd fills a zero "gradient" of act for every backward: 16 launches per step)
-            return y[0].view(*shp[:-1], y[0].shape[-1]), act
-        if stream:
-            ctx.set_materialize_grads(False)           # the lo image of the last block has no consumer: its gradient stays None
-            return y[0].view(*shp[:-1], y[0].shape[-1]), y[1].view(*shp[:-1], y[1].shape[-1])
+        ctx.has_res, ctx.has_lo = residual is not None, residual_lo is not None
+        if geglu or stream:
+            # geglu: else autograd fills a zero "gradient" of act for every backward (16 launches per step);
+            # stream: the lo image of the last block has no consumer, its gradient stays None
+            ctx.set_materialize_grads(False)
+            second = y[1].view(*shp[:-1], y[1].shape[-1])
+            if geglu:
+                ctx.mark_non_differentiable(second)
+            return y[0].view(*shp[:-1], y[0].shape[-1]), second
         return y.view(*shp[:-1], y.shape[-1])
 
     @staticmethod
     def backward(ctx, dy, dy_lo=None):
+        rest = (None,) * (len(ctx.needs_input_grad) - 3)
         if dy is None:                                 # (stream mode, nothing downstream took the gradient)
             assert dy_lo is None
-            return (None,) * 12
-        x2, T = ctx.saved_tensors
+            return (None, None, None) + rest
+        x2, T, hg2 = ctx.saved_tensors
         host, lora = ctx.host, ctx.lora
         dy2 = dy.reshape(-1, dy.shape[-1])
         if not dy2.is_contiguous():
             dy2 = dy2.contiguous()
         pk = host.packed()
-        dx = None
+        need, dx = ctx.needs_input_grad[0], None
         if lora is not None and getattr(lora, "wide", False):
             lp = lora.packed()
             U = K.gemm(dy2, lp.but)                    # dY (alpha W_up): [M, Rp]
-            if ctx.needs_input_grad[0]:
+            if need:
                 dx = K.gemm(dy2, pk.wt, a2=U, b2=lp.wdt)
             for blk, s0 in lora.members():             # one wide block, or several blocks sharing the wide slot range (lora.MultiLora)
-                gd, gu = blk.grad_views()
-                for j in range(0, blk.rank, 32):       # 32 rank columns per launch of the skinny reduction kernel
-                    pj = min(32, blk.rank - j)
-                    K.lora_wgrad(U[:, s0 + j:s0 + j + 32], x2, gd[j:j + pj], pj, 1.0, False)                # dW_down = U^T x
-                    K.lora_wgrad(T[:, s0 + j:s0 + j + 32], dy2, gu, pj, blk.alpha_f, True, out_col0=j)    # dW_up = alpha dY^T T
+                _lora_grads_wide(blk, s0, T, dy2, U, x2)
         elif lora is not None:
             lp = lora.packed()
-            if ctx.needs_input_grad[0]:
-                dx, U = K.gemm_lora(dy2, pk.wt, lp.but, lp.adt)
-            else:
+            if not need:
                 U = K.gemm(dy2, lp.but)
-            for blk, s0 in lora.members():             # one block, or several sharing the 32 rank slots (lora.MultiLora)
-                gd, gu = blk.grad_views()
-                ctx.wg.add(U, x2, gd, T, dy2, gu, blk.rank, blk.alpha_f, s0, K.t_lo(U), K.t_lo(T))
-        elif ctx.needs_input_grad[0]:
-            dx = K.gemm(dy2, pk.wt)
-        if ctx.train_w:                                # dW[N,K] += dY^T X (nn.Linear [N,K]; 1x1 conv [N,K,1,1] = same memory)
-            gw = grad_buffer(host.weight)
-            K.wgrad_linear(dy2, x2, gw.view(gw.shape[0], -1))
-        if ctx.train_b:
-            K.colsum(dy2, grad_buffer(host.bias))
+            elif hg2 is not None:
+                dx, U = K.gemm_geglu_bwd(dy2, pk.wt, hg2, l=lp.but, e=lp.adt)
+            else:
+                dx, U = K.gemm_lora(dy2, pk.wt, lp.but, lp.adt)
+            _lora_grads(ctx.wg, U, x2, T, dy2, lora.members(), K.t_lo(U), K.t_lo(T))
+        elif need:
+            dx = K.gemm_geglu_bwd(dy2, pk.wt, hg2)[0] if hg2 is not None else K.gemm(dy2, pk.wt)
+        _host_grads(ctx, host, dy2, x2)
         if dx is not None:
             dx = dx.view(ctx.xshape)
         # the stream's gradient is a (hi | lo) pair as well: the GEMMs above read its hi image (the reference's autograd casts the fp32
         # stream gradient to bf16 in front of the same mm), the residual path hands both images on untouched
-        return dx, (dy if ctx.has_res else None), None, None, None, None, None, None, None, (dy_lo if ctx.has_lo else None), None, None
+        return (dx, dy if ctx.has_res else None, dy_lo if ctx.has_lo else None) + rest
+
+
+def _linear(x, host, lora, residual=None, residual_lo=None, gact=None, out_f32=False, stream=False, kind=None):
+    return _LinearFn.apply(x, residual, residual_lo, gact, *_factors(lora), _tr(host.weight), _tr(host.bias), (host, lora, out_f32, stream, kind))
 
 
 def linear_geglu(x, host, lora=None):
     """((h | g), bf16(h * gelu(g))) of diffusers' GEGLU projection in one launch; hand both to geglu_linear."""
-    wd = lora.layer.W_down if lora is not None else None
-    wu = lora.layer.W_up if lora is not None else None
-    return _LinearFn.apply(x, None, wd, wu, host, lora, False, _tr(host.weight), _tr(host.bias), None, False, True)
+    return _linear(x, host, lora, kind="proj")
 
 
 def linear(x, host, lora=None, residual=None, out_f32=False):
-    wd = lora.layer.W_down if lora is not None else None
-    wu = lora.layer.W_up if lora is not None else None
-    hw, hb = _tr(host.weight), _tr(host.bias)
-    if out_f32 and (lora is not None or x.requires_grad or hw is not None or hb is not None):
+    if out_f32 and (lora is not None or x.requires_grad or _tr(host.weight) is not None or _tr(host.bias) is not None):
         raise NotImplementedError("hcp_diffusion_amd: fp32 linear output is only provided for the gradient-free time-embedding path")
-    return _LinearFn.apply(x, residual, wd, wu, host, lora, out_f32, hw, hb)
+    return _linear(x, host, lora, residual, out_f32=out_f32)
 
 
 def linear_stream(x, host, lora, hi, lo):
     """(y_hi, y_lo) = split(x W^T [+ LoRA] + bias + hi + lo): a Linear whose residual is a (hi | lo) residual stream (lo: None where the
     stream starts).  See GemmParams::residual_lo (csrc/gemm_params.h)."""
-    wd = lora.layer.W_down if lora is not None else None
-    wu = lora.layer.W_up if lora is not None else None
-    return _LinearFn.apply(x, hi, wd, wu, host, lora, False, _tr(host.weight), _tr(host.bias), lo, True)
+    return _linear(x, host, lora, hi, lo, stream=True)
+
+
+def geglu_linear(hg, host, lora=None, residual=None, gact=None):
+    """residual: a tensor, or the (hi, lo) pair of a (hi | lo) residual stream — the result is then a pair too.
+    gact: the second output of linear_geglu (the GEGLU product from the projection's own epilogue)."""
+    if isinstance(residual, tuple):
+        return _linear(hg, host, lora, residual[0], residual[1], gact, stream=True, kind="ff")
+    return _linear(hg, host, lora, residual, gact=gact, kind="ff")
 
 
 class _LinearGroupFn(torch.autograd.Function):
@@ -262,10 +313,7 @@ class _LinearGroupFn(torch.autograd.Function):
                 dx, U = K.gemm_lora(dy2, wt, o.but, o.adt)
             else:
                 U = K.gemm(dy2, o.but)
-            for blk, n0, s0, host, sc_ in zip(g.blocks, g.n_off, g.slot_off, g.hosts, g.out_scale):
-                if blk is not None:
-                    gd, gu = blk.grad_views()
-                    ctx.wg.add(U, x2, gd, T, dy2[:, n0:n0 + host.weight.shape[0]], gu, blk.rank, blk.alpha_f * sc_, s0, K.t_lo(U), K.t_lo(T))
+            _lora_grads_group(ctx.wg, U, x2, T, dy2, g, K.t_lo(U), K.t_lo(T))
         elif ctx.needs_input_grad[0]:
             dx = K.gemm(dy2, wt)
         if dx is not None:
@@ -320,11 +368,7 @@ class _CtxKVFn(torch.autograd.Function):
             sl = dall[:, off:off + g.n_total]
             U = U_all[:, 32 * gi:32 * gi + 32] if joint else K.gemm(sl, g.bucket.packed_group(g).but)
             T = T_all[:, 32 * gi:32 * gi + 32]
-            for blk, n0, s0, host, sc_ in zip(g.blocks, g.n_off, g.slot_off, g.hosts, g.out_scale):
-                if blk is not None:
-                    gd, gu = blk.grad_views()
-                    ctx.wg.add(U, x2, gd, T, sl[:, n0:n0 + host.weight.shape[0]], gu, blk.rank, blk.alpha_f * sc_, s0,
-                               batch.k2 if (joint and batch.split) else 0, batch.k2 if batch.split else 0)
+            _lora_grads_group(ctx.wg, U, x2, T, sl, g, batch.k2 if (joint and batch.split) else 0, batch.k2 if batch.split else 0)
         return (None, None) + (None,) * (len(ctx.needs_input_grad) - 2)
 
 
@@ -353,9 +397,10 @@ class _Conv3x3Fn(torch.autograd.Function):
     input (channel concat), stride 2, fused nearest-2x upsample."""
 
     @staticmethod
-    def forward(ctx, x1, x2, rowbias, residual, host, stride, upsample, hw=None, hb=None, lora=None, w_down=None, w_up=None):
+    def forward(ctx, x1, x2, rowbias, residual, w_down, w_up, hw, hb, opt):
+        host, lora, stride, upsample = opt
         pk = host.packed()
-        T = None
+        T, ctx.fold = None, False
         if lora is not None and getattr(lora, "wide", False):      # rank > 32: the side path's product joins through one more GEMM
             lp = lora.packed()
             rp = lora.rank_pad
@@ -370,9 +415,8 @@ class _Conv3x3Fn(torch.autograd.Function):
         else:
             # a FROZEN upsampler conv (LoRA / ControlNet training, inference) runs folded: 2x2 taps per output parity, 4/9 of the MFMA work
             # (layers.HipConv2d.folded); trained weights, LoRA-wrapped convs and other shapes keep the 3x3 gather
-            fold = (upsample and stride == 1 and x2 is None and rowbias is None and residual is None and not host.weight.requires_grad
-                    and K.conv_fold_eligible(pk.cin, pk.cout))
-            ctx.fold = fold
+            ctx.fold = fold = (upsample and stride == 1 and x2 is None and rowbias is None and residual is None
+                               and not host.weight.requires_grad and K.conv_fold_eligible(pk.cin, pk.cout))
             y = K.conv3x3(x1, pk.w, pk.cout, x2=x2, stride=stride, upsample=upsample, bias=pk.bias, rowbias=rowbias, residual=residual,
                           fold=host.folded()[0] if fold else None)
         ctx.host, ctx.stride, ctx.upsample, ctx.lora = host, stride, upsample, lora
@@ -398,17 +442,14 @@ class _Conv3x3Fn(torch.autograd.Function):
             lp = lora.packed()
             rp = lp.but.shape[0]                       # 32 rank slots, or the padded rank of a wide block
             U = K.gemm(dy.view(-1, dy.shape[-1]), lp.but).view(*dy.shape[:-1], rp)
-            T2 = T.view(-1, rp)
             for blk, s0 in lora.members():             # one block, or several sharing the 32 rank slots (lora.MultiLora)
-                gd, gu = blk.grad_views()
-                for j in range(0, blk.rank, 32):       # dW_up = alpha dY^T T: 32 rank columns per launch of the skinny reduction kernel
-                    K.lora_wgrad(T2[:, s0 + j:], dy.view(-1, dy.shape[-1]), gu, min(32, blk.rank - j), blk.alpha_f, True, out_col0=j)
+                gd = _lora_grads_wide(blk, s0, T.view(-1, rp), dy.view(-1, dy.shape[-1]))
                 K.wgrad_conv3x3(U, x1, gd, x2=x2, stride=ctx.stride, upsample=ctx.upsample, cout=blk.rank, col0=s0)
             if ctx.needs_input_grad[0]:
                 dl1 = K.conv3x3(U, lp.wdl[:C1], C1, mode=1, stride=ctx.stride, out_hw=hw)
             if ctx.c2 and ctx.needs_input_grad[1]:
                 dl2 = K.conv3x3(U, lp.wdl[C1:], ctx.c2, mode=1, stride=ctx.stride, out_hw=hw)
-        if ctx.needs_input_grad[0] and getattr(ctx, "fold", False):
+        if ctx.needs_input_grad[0] and ctx.fold:
             dx1 = K.conv3x3(dy, pk.wd[:C1], C1, mode=1, stride=ctx.stride, out_hw=hw, fold=ctx.host.folded()[1])   # low-resolution dX directly
         elif ctx.needs_input_grad[0]:
             dx1 = K.conv3x3(dy, pk.wd[:C1], C1, mode=1, stride=ctx.stride, out_hw=hw, residual=dl1)
@@ -421,22 +462,12 @@ class _Conv3x3Fn(torch.autograd.Function):
         if ctx.needs_input_grad[2]:                    # per-sample row bias (time embedding): sum over the sample's pixels
             drb = torch.zeros((B, dy.shape[-1]), dtype=torch.float32, device=dy.device)
             K.colsum(dy2, drb, dy.shape[1] * dy.shape[2])
-        if ctx.train_w:
-            K.wgrad_conv3x3(dy, x1, grad_buffer(ctx.host.weight, True), x2=x2, stride=ctx.stride, upsample=ctx.upsample)
-        if ctx.train_b:
-            K.colsum(dy2, grad_buffer(ctx.host.bias))
-        return dx1, dx2, drb, (dy if ctx.has_res else None), None, None, None, None, None, None, None, None
+        _conv_param_grads(ctx, dy, pk, x1, x2, ctx.stride, ctx.upsample)
+        return (dx1, dx2, drb, dy if ctx.has_res else None) + (None,) * (len(ctx.needs_input_grad) - 4)
 
 
 def conv3x3(x1, host, *, x2=None, rowbias=None, residual=None, stride=1, upsample=False, lora=None):
-    wd = lora.layer.W_down if lora is not None else None
-    wu = lora.layer.W_up if lora is not None else None
-    return _Conv3x3Fn.apply(x1, x2, rowbias, residual, host, stride, upsample, _tr(host.weight), _tr(host.bias), lora, wd, wu)
-
-
-def _gn_affine(ctx, x, dy, g, b, stats):
-    if ctx.train:
-        K.groupnorm_affine_grad(x, dy, g, b, stats, ctx.gn.num_groups, ctx.silu, grad_buffer(ctx.gn.weight), grad_buffer(ctx.gn.bias))
+    return _Conv3x3Fn.apply(x1, x2, rowbias, residual, *_factors(lora), _tr(host.weight), _tr(host.bias), (host, lora, stride, upsample))
 
 
 def _norm_tr(m):
@@ -447,119 +478,85 @@ def _norm_tr(m):
 
 
 class _GroupNormFn(torch.autograd.Function):
+    """norm(x), or with `fork` the pair (norm(x), x): the block input forks into the normalised branch and the residual path.  Backward then
+    receives both gradients at once and adds the residual-path one inside the norm-backward kernel (no separate accumulation)."""
+
     @staticmethod
-    def forward(ctx, x, gn, silu, hw=None, hb=None):
+    def forward(ctx, x, hw, hb, gn, silu, fork):
         g, b = gn.f32_params()
         y, stats = K.groupnorm_fwd(x, g, b, gn.num_groups, gn.eps, silu)
         ctx.save_for_backward(x, stats)
-        ctx.gn, ctx.silu, ctx.train = gn, silu, hw is not None
-        return y
+        ctx.gn, ctx.silu, ctx.train, ctx.fork = gn, silu, hw is not None, fork
+        return (y, x.view_as(x)) if fork else y
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, dskip=None):
+        rest = (None,) * (len(ctx.needs_input_grad) - 1)
         x, stats = ctx.saved_tensors
         g, b = ctx.gn.f32_params()
+        if dy is None:
+            return (dskip,) + rest
         dy = dy.contiguous()
-        _gn_affine(ctx, x, dy, g, b, stats)
-        dx = K.groupnorm_bwd(x, dy, g, b, stats, ctx.gn.num_groups, ctx.silu) if ctx.needs_input_grad[0] else None
-        return dx, None, None, None, None
+        if ctx.train:
+            K.groupnorm_affine_grad(x, dy, g, b, stats, ctx.gn.num_groups, ctx.silu, grad_buffer(ctx.gn.weight), grad_buffer(ctx.gn.bias))
+        if not (ctx.fork or ctx.needs_input_grad[0]):
+            return (None,) + rest
+        return (K.groupnorm_bwd(x, dy, g, b, stats, ctx.gn.num_groups, ctx.silu, dskip.contiguous() if dskip is not None else None),) + rest
 
 
 def groupnorm(x, gn, silu):
-    return _GroupNormFn.apply(x, gn, silu, *_norm_tr(gn))
-
-
-class _GroupNormForkFn(torch.autograd.Function):
-    """(norm(x), x): the block input forks into the normalised branch and the residual path.  Backward receives both
-    gradients at once and adds the residual-path one inside the norm-backward kernel (no separate accumulation)."""
-
-    @staticmethod
-    def forward(ctx, x, gn, silu, hw=None, hb=None):
-        g, b = gn.f32_params()
-        y, stats = K.groupnorm_fwd(x, g, b, gn.num_groups, gn.eps, silu)
-        ctx.save_for_backward(x, stats)
-        ctx.gn, ctx.silu, ctx.train = gn, silu, hw is not None
-        return y, x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, dy, dskip):
-        x, stats = ctx.saved_tensors
-        g, b = ctx.gn.f32_params()
-        if dy is None:
-            return dskip, None, None, None, None
-        dy = dy.contiguous()
-        _gn_affine(ctx, x, dy, g, b, stats)
-        return K.groupnorm_bwd(x, dy, g, b, stats, ctx.gn.num_groups, ctx.silu,
-                               dskip.contiguous() if dskip is not None else None), None, None, None, None
+    return _GroupNormFn.apply(x, *_norm_tr(gn), gn, silu, False)
 
 
 def groupnorm_fork(x, gn, silu):
-    return _GroupNormForkFn.apply(x, gn, silu, *_norm_tr(gn))
+    return _GroupNormFn.apply(x, *_norm_tr(gn), gn, silu, True)
 
 
 class _LayerNormFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, ln, hw=None, hb=None):
-        g, b = ln.f32_params()
-        y, stats = K.layernorm_fwd(x, g, b, ln.eps)
-        ctx.save_for_backward(x, stats)
-        ctx.ln, ctx.train = ln, hw is not None
-        return y
+    """layer_norm(x); with `fork` (layer_norm(x), x) for pre-norm residual blocks, see _GroupNormFn; with `stream` on top x is the hi image
+    of a (hi | lo) residual stream and x_lo its lo image (None where the stream starts): returns (LN(x + x_lo), x, x_lo) and takes the
+    skip gradient back as a pair."""
 
     @staticmethod
-    def backward(ctx, dy):
-        x, stats = ctx.saved_tensors
-        g, _ = ctx.ln.f32_params()
-        dy = dy.contiguous()
-        if ctx.train:
-            K.layernorm_affine_grad(x, dy, stats, grad_buffer(ctx.ln.weight), grad_buffer(ctx.ln.bias))
-        return (K.layernorm_bwd(x, dy, g, stats) if ctx.needs_input_grad[0] else None), None, None, None
-
-
-def layernorm(x, ln):
-    return _LayerNormFn.apply(x, ln, *_norm_tr(ln))
-
-
-class _LayerNormForkFn(torch.autograd.Function):
-    """(layer_norm(x), x) for pre-norm residual blocks; see _GroupNormForkFn."""
-
-    @staticmethod
-    def forward(ctx, x, ln, hw=None, hb=None, x_lo=None, stream=False):
-        """stream: x is the hi image of a (hi | lo) residual stream, x_lo its lo image (None where the stream starts); returns
-        (LN(x + x_lo), x, x_lo) and takes the skip gradient back as a pair."""
+    def forward(ctx, x, x_lo, hw, hb, ln, fork, stream):
         g, b = ln.f32_params()
         y, stats = K.layernorm_fwd(x, g, b, ln.eps, x_lo=x_lo)
         ctx.save_for_backward(x, stats, x_lo)
-        ctx.ln, ctx.train, ctx.stream = ln, hw is not None, stream
+        ctx.ln, ctx.train, ctx.fork = ln, hw is not None, fork
         if stream:
             ctx.set_materialize_grads(False)
             return y, x.view_as(x), (x_lo.view_as(x_lo) if x_lo is not None else None)
-        return y, x.view_as(x)
+        return (y, x.view_as(x)) if fork else y
 
     @staticmethod
-    def backward(ctx, dy, dskip, dskip_lo=None):
+    def backward(ctx, dy, dskip=None, dskip_lo=None):
+        rest = (None,) * (len(ctx.needs_input_grad) - 2)
         x, stats, x_lo = ctx.saved_tensors
         g, _ = ctx.ln.f32_params()
         if dy is None:
-            return dskip, None, None, None, dskip_lo, None
+            return (dskip, dskip_lo) + rest
         dy = dy.contiguous()
         if ctx.train:
             K.layernorm_affine_grad(x, dy, stats, grad_buffer(ctx.ln.weight), grad_buffer(ctx.ln.bias))
-        if ctx.stream:
-            want_lo = x_lo is not None                 # the stream's first norm hands ONE bf16 gradient back to the producer of x
-            r = K.layernorm_bwd(x, dy, g, stats, dskip.contiguous() if dskip is not None else None, x_lo=x_lo,
-                                addend_lo=dskip_lo.contiguous() if (dskip_lo is not None and dskip is not None) else None, want_lo=want_lo)
-            return (r[0], None, None, None, r[1], None) if want_lo else (r, None, None, None, None, None)
-        return K.layernorm_bwd(x, dy, g, stats, dskip.contiguous() if dskip is not None else None), None, None, None, None, None
+        if not (ctx.fork or ctx.needs_input_grad[0]):
+            return (None, None) + rest
+        want_lo = x_lo is not None                     # (stream only) the stream's first norm hands ONE bf16 gradient back to the producer of x
+        r = K.layernorm_bwd(x, dy, g, stats, dskip.contiguous() if dskip is not None else None, x_lo=x_lo,
+                            addend_lo=dskip_lo.contiguous() if (dskip_lo is not None and dskip is not None) else None, want_lo=want_lo)
+        return (r if want_lo else (r, None)) + rest
+
+
+def layernorm(x, ln):
+    return _LayerNormFn.apply(x, None, *_norm_tr(ln), ln, False, False)
 
 
 def layernorm_fork(x, ln):
-    return _LayerNormForkFn.apply(x, ln, *_norm_tr(ln))
+    return _LayerNormFn.apply(x, None, *_norm_tr(ln), ln, True, False)
 
 
 def layernorm_fork_stream(hi, lo, ln):
     """(LN(hi + lo), hi, lo) on a (hi | lo) residual stream; lo may be None (the stream's first norm)."""
-    return _LayerNormForkFn.apply(hi, ln, *_norm_tr(ln), lo, True)
+    return _LayerNormFn.apply(hi, lo, *_norm_tr(ln), ln, True, True)
 
 
 class _GegluFn(torch.autograd.Function):
@@ -575,83 +572,6 @@ class _GegluFn(torch.autograd.Function):
 
 
 geglu = _GegluFn.apply
-
-
-class _GegluLinearFn(torch.autograd.Function):
-    """y = FFout(h * gelu(g)) (+ residual) for (h | g) = hg, i.e. diffusers' FeedForward after its first projection
-    (GEGLU + Dropout(0) + Linear, cfgs/unet_struct.txt:27-33) as ONE autograd node: the forward is the GEGLU kernel + the (fused-LoRA) GEMM
-    as before; the backward runs the input-gradient GEMM with the GEGLU backward in its epilogue (hcp_gemm_geglu_bwd_bf16) — the
-    [M, 4C] gradient of the GEGLU output is never written or re-read, and the stand-alone geglu_bwd launch is gone.  Same arithmetic as
-    _GegluFn + _LinearFn (the epilogue rounds dY_ff to bf16 before the two products, as the two-kernel form does)."""
-
-    @staticmethod
-    def forward(ctx, hg, residual, w_down, w_up, host, lora, hw=None, hb=None, residual_lo=None, stream=False, gact=None):
-        """gact: bf16(h * gelu(g)) already formed by the projection's epilogue (linear_geglu), else the stand-alone pass runs here."""
-        shp = hg.shape
-        hg2 = hg.reshape(-1, shp[-1])
-        x2 = gact.reshape(-1, gact.shape[-1]) if gact is not None else K.geglu_fwd(hg2)
-        res2 = residual.reshape(-1, residual.shape[-1]) if residual is not None else None
-        lo2 = residual_lo.reshape(-1, residual_lo.shape[-1]) if residual_lo is not None else None
-        pk = host.packed()
-        T = None
-        if lora is not None:
-            lp = lora.packed()
-            y, T = K.gemm_lora(x2, pk.w, lp.ad, lp.bu, bias=pk.bias, residual=res2, residual_lo=lo2, want_lo=stream)
-        else:
-            y = K.gemm(x2, pk.w, bias=pk.bias, residual=res2, residual_lo=lo2, want_lo=stream)
-        ctx.host, ctx.lora = host, lora
-        ctx.wg = current_wgrad()
-        ctx.train_w, ctx.train_b = hw is not None, hb is not None
-        ctx.save_for_backward(hg2, x2 if (lora is not None or hw is not None) else None, T)
-        ctx.hshape = shp
-        ctx.has_res = residual is not None
-        ctx.has_lo = residual_lo is not None
-        if stream:                                     # (hi | lo) residual stream: see _LinearFn
-            ctx.set_materialize_grads(False)
-            return y[0].view(*shp[:-1], y[0].shape[-1]), y[1].view(*shp[:-1], y[1].shape[-1])
-        return y.view(*shp[:-1], y.shape[-1])
-
-    @staticmethod
-    def backward(ctx, dy, dy_lo=None):
-        if dy is None:
-            assert dy_lo is None
-            return (None,) * 11
-        hg2, x2, T = ctx.saved_tensors
-        host, lora = ctx.host, ctx.lora
-        dy2 = dy.reshape(-1, dy.shape[-1])
-        if not dy2.is_contiguous():
-            dy2 = dy2.contiguous()
-        pk = host.packed()
-        dhg = None
-        if lora is not None:
-            lp = lora.packed()
-            if ctx.needs_input_grad[0]:
-                dhg, U = K.gemm_geglu_bwd(dy2, pk.wt, hg2, l=lp.but, e=lp.adt)
-            else:
-                U = K.gemm(dy2, lp.but)
-            for blk, s0 in lora.members():
-                gd, gu = blk.grad_views()
-                ctx.wg.add(U, x2, gd, T, dy2, gu, blk.rank, blk.alpha_f, s0, K.t_lo(U), K.t_lo(T))
-        elif ctx.needs_input_grad[0]:
-            dhg, _ = K.gemm_geglu_bwd(dy2, pk.wt, hg2)
-        if ctx.train_w:
-            gw = grad_buffer(host.weight)
-            K.wgrad_linear(dy2, x2, gw.view(gw.shape[0], -1))
-        if ctx.train_b:
-            K.colsum(dy2, grad_buffer(host.bias))
-        if dhg is not None:
-            dhg = dhg.view(ctx.hshape)
-        return dhg, (dy if ctx.has_res else None), None, None, None, None, None, None, (dy_lo if ctx.has_lo else None), None, None
-
-
-def geglu_linear(hg, host, lora=None, residual=None, gact=None):
-    """residual: a tensor, or the (hi, lo) pair of a (hi | lo) residual stream — the result is then a pair too.
-    gact: the second output of linear_geglu (the GEGLU product from the projection's own epilogue)."""
-    wd = lora.layer.W_down if lora is not None else None
-    wu = lora.layer.W_up if lora is not None else None
-    if isinstance(residual, tuple):
-        return _GegluLinearFn.apply(hg, residual[0], wd, wu, host, lora, _tr(host.weight), _tr(host.bias), residual[1], True, gact)
-    return _GegluLinearFn.apply(hg, residual, wd, wu, host, lora, _tr(host.weight), _tr(host.bias), None, False, gact)
 
 
 class _AttentionFn(torch.autograd.Function):
@@ -897,16 +817,15 @@ class _ConvOutFn(torch.autograd.Function):
         pk = ctx.host.packed()
         B, H, W, C = ctx.in_shape
         g = K.nchw_to_nhwc(dy.contiguous(), pk.cout_pad)
-        _conv_param_grads(ctx, g, pk)
+        _conv_param_grads(ctx, g, pk, *ctx.saved_tensors)
         dx = K.conv3x3(g, pk.wd, C, mode=1, stride=1, out_hw=(H, W)) if ctx.needs_input_grad[0] else None
         return dx, None, None, None
 
 
-def _conv_param_grads(ctx, g, pk):
-    """Weight / bias gradients of a 3x3 conv whose output gradient `g` is channel-padded NHWC bf16."""
+def _conv_param_grads(ctx, g, pk, x1=None, x2=None, stride=1, upsample=False):
+    """Weight / bias gradients of a 3x3 conv whose output gradient `g` is (channel-padded) NHWC bf16; x1 / x2: the forward's inputs."""
     if ctx.train_w:
-        (x,) = ctx.saved_tensors
-        K.wgrad_conv3x3(g, x, grad_buffer(ctx.host.weight, True), cout=pk.cout)
+        K.wgrad_conv3x3(g, x1, grad_buffer(ctx.host.weight, True), x2=x2, stride=stride, upsample=upsample, cout=pk.cout)
     if ctx.train_b:
         gb = grad_buffer(ctx.host.bias)
         if g.shape[-1] == pk.cout:
@@ -936,7 +855,7 @@ class _ConvInFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        _conv_param_grads(ctx, dy.contiguous(), ctx.host.packed())
+        _conv_param_grads(ctx, dy.contiguous(), ctx.host.packed(), *ctx.saved_tensors)
         return None, None, None, None
 
 

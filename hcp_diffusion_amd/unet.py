@@ -271,7 +271,7 @@ class FeedForward(nn.Module):
         leaf = _ff_out_leaf(self.net[2]) if not (self.net[0]._forward_hooks or self.net[0]._forward_pre_hooks) and self.net[1].p == 0.0 else None
         if leaf is not None and type(self.net[0]) is GEGLU:
             # GEGLU + output projection as one autograd node: the GEGLU backward rides in the epilogue of the projection's
-            # input-gradient GEMM (ops._GegluLinearFn).  A hooked / foreign / dropout leaf keeps the module-by-module path below.
+            # input-gradient GEMM (ops.geglu_linear: ops._LinearFn, kind "ff").  A hooked / foreign / dropout leaf keeps the module-by-module path below.
             pleaf = _ff_out_leaf(self.net[0].proj) if self.geglu_in_epilogue else None
             if pleaf is not None:
                 # OPT-IN (FeedForward.geglu_in_epilogue / unet.set_geglu_epilogue): the GEGLU product out of the PROJECTION's epilogue,

@@ -167,13 +167,13 @@ def _upsampler(cin, cout, dev, seed=21):
 
 def _run_module(m, x, dy):
     xi = x.clone().requires_grad_(True)
-    K.TRACE = []
+    K.LAUNCHES = []
     try:
         y = m(xi)
         y.backward(dy)
-        trace = list(K.TRACE)
+        trace = [k for k in map(K.trace_key, K.LAUNCHES) if k is not None]
     finally:
-        K.TRACE = None
+        K.LAUNCHES = None
     return y.detach().cpu(), xi.grad.detach().cpu(), trace
 
 

@@ -557,6 +557,43 @@ def test_layernorm(backend, M, C):
     assert relerr(K.layernorm_bwd(to(x), to(dy), to(gamma), stats, addend=to(skip)), xr.grad + skip.float()) < 1e-2
 
 
+@pytest.mark.parametrize("kind", ["group", "layer"])
+def test_ops_norm_with_trainable_affine_on_an_input_without_gradient(backend, kind, monkeypatch):
+    """ops.groupnorm / ops.layernorm (not the fork form) on an input that needs no gradient, affine parameters trainable: the node runs for
+    the parameters alone — their gradients land in the fp32 ``.grad``, and the input-gradient kernel is not launched.  Against float64."""
+    from hcp_diffusion_amd.layers import HipGroupNorm, HipLayerNorm
+    torch.manual_seed(7)
+    to = backend.to
+    C = 64
+    m, x = (HipGroupNorm(32, C), (torch.randn(2, 8, 8, C) * 2 + 0.7).to(BF)) if kind == "group" else (HipLayerNorm(C), (torch.randn(128, C) * 3 + 1).to(BF))
+    with torch.no_grad():
+        m.weight.copy_(torch.randn(C) * 0.5 + 1); m.bias.copy_(torch.randn(C) * 0.3)
+    m.to(backend.device)
+    dy = rnd(*x.shape)
+    launched = []
+    name = "groupnorm_bwd" if kind == "group" else "layernorm_bwd"
+    orig = getattr(K, name)
+    monkeypatch.setattr(K, name, lambda *a, **k: (launched.append(name), orig(*a, **k))[1])
+    y = m(to(x), silu=True) if kind == "group" else m(to(x))
+    y.backward(to(dy))
+    assert not launched
+    w, b = m.weight.detach().cpu().double().requires_grad_(True), m.bias.detach().cpu().double().requires_grad_(True)
+    xr = x.double().requires_grad_(True)                     # (the restatement differentiates its input too, like its neighbours above)
+    if kind == "group":
+        yr = F.silu(F.group_norm(xr.permute(0, 3, 1, 2), 32, w, b, m.eps)).permute(0, 2, 3, 1)
+    else:
+        yr = F.layer_norm(xr, (C,), w, b, m.eps)
+    yr.backward(dy.double())
+    assert m.weight.grad.dtype == torch.float32
+    # the bounds of the kernel-level tests above: y is stored as bf16 (2^-9 relative rounding per element on top of the bf16 input's),
+    # the parameter gradients are fp32 sums over all rows, in which that rounding averages out
+    assert relerr(m.weight.grad, w.grad) < 2e-3 and relerr(m.bias.grad, b.grad) < 2e-3
+    assert relerr(y, yr) < 1e-2
+    xg = to(x).requires_grad_(True)                          # control: the same node on an input that wants its gradient goes through the patched name
+    (m(xg, silu=True) if kind == "group" else m(xg)).backward(to(dy))
+    assert launched == [name] and relerr(xg.grad, xr.grad) < 1e-2
+
+
 @pytest.mark.parametrize("M,Fd", [(9, 64), (33, 1280), (16384, 1280)])
 def test_geglu(backend, M, Fd):
     if not backend.is_gpu and M > 100:

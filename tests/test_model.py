@@ -1311,12 +1311,12 @@ def test_batched_cross_attention_kv_matches_the_per_layer_projections(backend, v
         if not batched:
             nat._batched_ctx_kv = lambda ctx: None
         tr.make_noise = lambda lat: (Kn.add_noise(lat, backend.to(noise), backend.to(t), tr.acp), backend.to(noise), backend.to(t))
-        Kn.TRACE = []
+        Kn.LAUNCHES = []
         try:
             loss = tr.forward_backward(backend.to(x0), backend.to(ehs), attn_mask=backend.to(mask) if mask is not None else None)
-            trace = list(Kn.TRACE)
+            trace = [k for k in map(Kn.trace_key, Kn.LAUNCHES) if k is not None]
         finally:
-            Kn.TRACE = None
+            Kn.LAUNCHES = None
         res[batched] = (loss.item(), tr.bucket.grads.detach().float().cpu().clone(), len(trace))
         if batched:
             n_layers = sum(1 for n, _ in nat.named_modules() if n.endswith(".attn2"))

@@ -2,8 +2,8 @@
 
   python tools/autotune.py sdxl|dreambooth|controlnet|sd15 [batch]
 
-One eager training step runs with kernels.TRACE recording every GEMM / fused-LoRA GEMM / implicit-conv launch; every distinct
-shape is then swept over all tile configurations and split-K factors through the tuning hook, and the winners are written to
+One eager training step runs with kernels.LAUNCHES recording every launch; every distinct GEMM / fused-LoRA GEMM / implicit-conv
+shape (kernels.trace_key) is then swept over all tile configurations and split-K factors through the tuning hook, and the winners are written to
 gpurun_out/tune_extra_<workload>.json.  tools/gen_gemm_table.py merges tools/tune_extra_*.json into csrc/gemm_tuned.inc."""
 import collections
 import json
@@ -60,10 +60,10 @@ def trace(workload, B):
     tr, lat, ehs, kw = setup(workload, B, dev)
     tr.train_one_step(lat, ehs, **kw)          # warm-up (lazy packing)
     K.lib().hcp_debug_gemm_table_stats(None, None)
-    K.TRACE = []
+    K.LAUNCHES = []
     tr.train_one_step(lat, ehs, **kw)
-    keys = collections.Counter(K.TRACE)
-    K.TRACE = None
+    keys = collections.Counter(k for k in map(K.trace_key, K.LAUNCHES) if k is not None)
+    K.LAUNCHES = None
     import ctypes
     h, m = ctypes.c_long(), ctypes.c_long()
     K.lib().hcp_debug_gemm_table_stats(ctypes.byref(h), ctypes.byref(m))

@@ -6,7 +6,7 @@ issue the tile's LDS-DMA, the compute waves only read fragments and issue MFMAs)
 --pp (round 4): sweep the ping-pong kernel (csrc/gemm_pp.hip: two compute groups half a phase apart, K-split, LDS ring 3 / 4) on the
 same tile ids against the FULL current dispatch (main + loader tables) -> gpurun_out/tune_pp_<workload>.json.
 
-Traces one training step (kernels.TRACE), then for every distinct shape times the CURRENT dispatch against tile ids 13 / 14 / 15
+Traces one training step (kernels.LAUNCHES / kernels.trace_key), then for every distinct shape times the CURRENT dispatch against tile ids 13 / 14 / 15
 (128x160, 64x160, 128x128 with 8 compute waves) x split-K with loaders forced on.  Winners by > 3 % go to
 gpurun_out/tune_loaders_<workload>.json; tools/gen_loader_table.py turns tools/tune_loaders_*.json into csrc/gemm_tuned_loaders.inc
 (looked up before the main table).
