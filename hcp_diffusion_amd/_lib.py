@@ -88,6 +88,11 @@ _PROTOTYPES = {
     "hcp_embedding_pt_fwd_bf16": (I, [P, I, I, I, I, P, I, P, P, I, P, I, P, I, P, P, I, P]),
     # dX, src_map, M, C, grad, n_custom, beta, stream
     "hcp_embedding_pt_bwd_f32": (I, [P, P, L, I, P, I, I, P]),
+    "hcp_gelu": (I, [P, P, P, L, P]),
+    # x, ids, gamma, beta, W, w_is_f32, pooled, positions, stats, B, R, L, C, P, eps, stream
+    "hcp_clip_pool_fwd": (I, [P, P, P, P, P, I, P, P, P, I, I, I, I, I, F, P]),
+    # x, positions, stats, gamma, W, w_is_f32, d_pooled, dx, B, R, L, C, P, stream
+    "hcp_clip_pool_bwd": (I, [P, P, P, P, P, I, P, P, I, I, I, I, I, P]),
     "hcp_transpose_bf16": (I, [P, P, I, I, I, P]),
     "hcp_softmax_rows": (I, [P, L, P, L, I, I, F, P]),
     "hcp_vae_latent_sample": (I, [P, P, P, P, P, I, I, L, F, P]),
@@ -137,7 +142,7 @@ TOOLS_SYMBOLS = tuple(_TOOLS_PROTOTYPES)
 TOOLS_LIB_PATH = Path(__file__).resolve().parent / "libhcp_mi355x_tools.so"
 
 
-ABI_VERSION = 5          # include/hcp_mi355x.h HCP_ABI_VERSION: bumped whenever an exported signature or descriptor layout changes
+ABI_VERSION = 6         # include/hcp_mi355x.h HCP_ABI_VERSION: bumped whenever an exported signature or descriptor layout changes
 
 
 class HcpError(RuntimeError):

@@ -12,6 +12,8 @@
 //
 // Ids at or above `vocab` without a registered word (map entry absent, n_vec <= 0, or outside the custom table) and negative ids read
 // the clipped token row, as the reference's table lookup does before its hook replaces the row; nothing is ever read out of bounds.
+//
+// Second half of the file: the other end of the text encoder — the pooled projection of CLIPTextModelWithProjection (clip_pool_*).
 #include "hcp_common.h"
 
 namespace {
@@ -126,7 +128,186 @@ HCP_KERNEL(256) embedding_pt_bwd_kernel(const hcp_bf16* dx, const int* src_map, 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Pooled projection of CLIPTextModelWithProjection (SDXL's second encoder): text_projection(final_layer_norm(last_hidden)[eos]),
+// averaged over the r chunks of one prompt (TEEXHook.forward_hook, textencoder_ex.py:73-76).  B*r is a handful of rows: a GEMV per
+// prompt.  The projection is linear, so the r normalised EOS tokens are averaged FIRST (fp32, in LDS) and multiplied once.
+//  * forward:  workgroup (prompt b, 16 output columns).  Per chunk: first position of the maximum id (transformers' rule for
+//              eos_token_id == 2), two-pass LayerNorm statistics of that one token, xbar += LN(token) / r.  Then each wave forms its
+//              columns' dot products with 16-byte weight loads and a wave sum.  Every output is written by exactly one lane.
+//  * backward: workgroup = one row m = b*r + k.  g = W^T d_pooled[b] / r (8 partial sums over P per column, added in a fixed order),
+//              LayerNorm backward of g at the EOS token, and the rest of dx[m] is cleared by the same workgroup: dx is WRITTEN.
+constexpr int CP_THREADS = 256;
+constexpr int CP_PSLICE = 16;
+constexpr int CP_MAX = 8192;
+
+HCP_DEVICE float cp_block_sum(float v, float* red) {
+    v = hcp_wave_sum(v);
+    HCP_SYNC();                                  // red may still be read from the previous reduction
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    HCP_SYNC();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+// first position of the maximum of ids[0, L): the same value in every thread
+HCP_DEVICE int cp_first_argmax(const long long* ids, int L, long long* sv, int* si) {
+    const int tid = threadIdx.x;
+    long long best = 0; int bi = 0x7fffffff;
+    for (int i = tid; i < L; i += CP_THREADS) {  // increasing i: a strict > keeps the first
+        const long long v = ids[i];
+        if (bi == 0x7fffffff || v > best) { best = v; bi = i; }
+    }
+    sv[tid] = best; si[tid] = bi;
+    HCP_SYNC();
+    for (int s = CP_THREADS / 2; s >= 1; s >>= 1) {
+        if (tid < s) {
+            const long long o = sv[tid + s]; const int oi = si[tid + s];
+            const bool mine = si[tid] != 0x7fffffff;
+            if (oi != 0x7fffffff && (!mine || o > sv[tid] || (o == sv[tid] && oi < si[tid]))) { sv[tid] = o; si[tid] = oi; }
+        }
+        HCP_SYNC();
+    }
+    const int r = si[0];
+    HCP_SYNC();
+    return r;
+}
+
+HCP_DEVICE void cp_load_w8(const void* W, int w_f32, size_t off, float (&w)[8]) {
+    if (w_f32) {
+        const hcp_f32x4 a = *(const hcp_f32x4*)((const float*)W + off), b = *(const hcp_f32x4*)((const float*)W + off + 4);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { w[q] = a[q]; w[q + 4] = b[q]; }
+    } else {
+        const hcp_bf16x8 v = *(const hcp_bf16x8*)((const hcp_bf16*)W + off);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) w[q] = hcp_bf2f((unsigned short)v[q]);
+    }
+}
+
+HCP_KERNEL(256) clip_pool_fwd_kernel(const hcp_bf16* x, const long long* ids, const float* gamma, const float* beta, const void* W,
+                                     int w_f32, float* pooled, int* pos_out, float* stats, int R, int L, int C, int P, float eps) {
+    HCP_DYN_SMEM(smem);
+    float* xbar = (float*)smem;                  // [C] mean over the chunks of LN(eos token)
+    float* red = xbar + C;                       // [4]
+    long long* sv = (long long*)(red + 4);       // [CP_THREADS]
+    int* si = (int*)(sv + CP_THREADS);           // [CP_THREADS]
+    const int b = blockIdx.x, p0 = blockIdx.y * CP_PSLICE, tid = threadIdx.x;
+    const float inv_r = 1.0f / (float)R;
+    for (int c = tid; c < C; c += CP_THREADS) xbar[c] = 0.f;
+    for (int k = 0; k < R; ++k) {
+        const size_t m = (size_t)b * R + k;
+        const int pos = cp_first_argmax(ids + m * L, L, sv, si);
+        const hcp_bf16* tok = x + (m * L + pos) * C;
+        float s = 0.f;
+        for (int c = tid; c < C; c += CP_THREADS) s += hcp_bf2f(tok[c]);
+        const float mean = cp_block_sum(s, red) / (float)C;
+        float q = 0.f;
+        for (int c = tid; c < C; c += CP_THREADS) { const float d = hcp_bf2f(tok[c]) - mean; q += d * d; }
+        const float rstd = 1.0f / sqrtf(cp_block_sum(q, red) / (float)C + eps);
+        for (int c = tid; c < C; c += CP_THREADS) xbar[c] += ((hcp_bf2f(tok[c]) - mean) * rstd * gamma[c] + beta[c]) * inv_r;
+        if (blockIdx.y == 0 && tid == 0) { pos_out[m] = pos; stats[2 * m] = mean; stats[2 * m + 1] = rstd; }
+    }
+    HCP_SYNC();
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int j = wave; j < CP_PSLICE && p0 + j < P; j += CP_THREADS / 64) {
+        const int p = p0 + j;
+        float acc = 0.f;
+        for (int c = lane * 8; c < C; c += 64 * 8) {
+            float w[8];
+            cp_load_w8(W, w_f32, (size_t)p * C + c, w);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) acc += w[q] * xbar[c + q];
+        }
+        acc = hcp_wave_sum(acc);
+        if (lane == 0) pooled[(size_t)b * P + p] = acc;
+    }
+}
+
+HCP_KERNEL(256) clip_pool_bwd_kernel(const hcp_bf16* x, const int* pos_in, const float* stats, const float* gamma, const void* W, int w_f32,
+                                     const float* dpooled, hcp_bf16* dx, int R, int L, int C, int P) {
+    HCP_DYN_SMEM(smem);
+    float* g = (float*)smem;                     // [C] W^T d / r
+    float* d = g + C;                            // [P] d_pooled[b] / r
+    float* part = d + P;                         // [8][256] partial column sums over the 8 interleaved slices of P
+    float* red = part + 8 * CP_THREADS;          // [4]
+    const size_t m = blockIdx.x;
+    const int b = (int)(m / R), tid = threadIdx.x;
+    int pos = pos_in[m];
+    pos = pos < 0 ? 0 : (pos >= L ? L - 1 : pos);             // (never write outside the row, whatever the buffer holds)
+    const float inv_r = 1.0f / (float)R;
+    for (int p = tid; p < P; p += CP_THREADS) d[p] = dpooled[(size_t)b * P + p] * inv_r;
+    HCP_SYNC();
+    const int cl = tid & 31, ps = tid >> 5;
+    for (int c0 = 0; c0 < C; c0 += CP_THREADS) {
+        const int c = c0 + cl * 8;
+        float acc[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc[q] = 0.f;
+        if (c < C)
+            for (int p = ps; p < P; p += 8) {
+                float w[8];
+                cp_load_w8(W, w_f32, (size_t)p * C + c, w);
+                const float dp = d[p];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) acc[q] += w[q] * dp;
+            }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) part[ps * CP_THREADS + cl * 8 + q] = acc[q];
+        HCP_SYNC();
+        if (c0 + tid < C) {
+            float s = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s += part[j * CP_THREADS + tid];
+            g[c0 + tid] = s;
+        }
+        HCP_SYNC();
+    }
+    const float mean = stats[2 * m], rstd = stats[2 * m + 1];
+    const hcp_bf16* tok = x + (m * L + pos) * C;
+    float s1 = 0.f, s2 = 0.f;
+    for (int c = tid; c < C; c += CP_THREADS) {
+        const float dxn = g[c] * gamma[c], xh = (hcp_bf2f(tok[c]) - mean) * rstd;
+        s1 += dxn; s2 += dxn * xh;
+    }
+    s1 = cp_block_sum(s1, red) / (float)C;
+    s2 = cp_block_sum(s2, red) / (float)C;
+    hcp_bf16* drow = dx + m * L * C;
+    const int cv = C / 8;
+    const long nv = (long)L * cv;
+    for (long i = tid; i < nv; i += CP_THREADS)
+        if ((int)(i / cv) != pos) *(hcp_bf16x8*)(drow + i * 8) = hcp_zero8();
+    for (int c = tid; c < C; c += CP_THREADS) {
+        const float dxn = g[c] * gamma[c], xh = (hcp_bf2f(tok[c]) - mean) * rstd;
+        drow[(size_t)pos * C + c] = hcp_f2bf(rstd * (dxn - s1 - xh * s2));
+    }
+}
+
 }  // namespace
+
+HCP_API int hcp_clip_pool_fwd(const void* x, const long long* ids, const float* gamma, const float* beta, const void* W, int w_is_f32,
+                              float* pooled, int* positions, float* stats, int B, int R, int L, int C, int P, float eps,
+                              hipStream_t stream) {
+    HCP_REQUIRE(x && ids && gamma && beta && W && pooled && positions && stats, "hcp_clip_pool_fwd: null pointer");
+    HCP_REQUIRE(B > 0 && B < 65536 && R > 0 && L > 0 && C > 0 && C % 8 == 0 && C <= CP_MAX && P > 0 && P <= CP_MAX * CP_PSLICE && eps > 0.f,
+                "hcp_clip_pool_fwd: bad shape (C %% 8 == 0, C <= %d)", CP_MAX);
+    HCP_REQUIRE(((size_t)x | (size_t)W) % 16 == 0, "hcp_clip_pool_fwd: x and W must be 16-byte aligned");
+    const size_t smem = (size_t)(C + 4) * sizeof(float) + CP_THREADS * (sizeof(long long) + sizeof(int));
+    HCP_LAUNCH(clip_pool_fwd_kernel, dim3(B, hcp_cdiv(P, CP_PSLICE)), dim3(CP_THREADS), smem, stream, (const hcp_bf16*)x, ids, gamma, beta, W,
+               w_is_f32, pooled, positions, stats, R, L, C, P, eps);
+    HCP_LAUNCH_CHECK("clip_pool_fwd");
+}
+
+HCP_API int hcp_clip_pool_bwd(const void* x, const int* positions, const float* stats, const float* gamma, const void* W, int w_is_f32,
+                              const float* d_pooled, void* dx, int B, int R, int L, int C, int P, hipStream_t stream) {
+    HCP_REQUIRE(x && positions && stats && gamma && W && d_pooled && dx, "hcp_clip_pool_bwd: null pointer");
+    HCP_REQUIRE(B > 0 && R > 0 && (long)B * R < 65536 && L > 0 && C > 0 && C % 8 == 0 && P > 0 && C + P <= CP_MAX,
+                "hcp_clip_pool_bwd: bad shape (C %% 8 == 0, C + P <= %d)", CP_MAX);
+    HCP_REQUIRE(((size_t)x | (size_t)W | (size_t)dx) % 16 == 0, "hcp_clip_pool_bwd: x, W and dx must be 16-byte aligned");
+    const size_t smem = (size_t)(C + P + 8 * CP_THREADS + 4) * sizeof(float);
+    HCP_LAUNCH(clip_pool_bwd_kernel, dim3(B * R), dim3(CP_THREADS), smem, stream, (const hcp_bf16*)x, positions, stats, gamma, W, w_is_f32,
+               (const float*)d_pooled, (hcp_bf16*)dx, R, L, C, P);
+    HCP_LAUNCH_CHECK("clip_pool_bwd");
+}
 
 HCP_API int hcp_embedding_pt_fwd_bf16(const long long* ids, int B, int R, int W, int n_word, const float* token_table, int vocab,
                                       const float* position_table, const long long* position_ids, int n_pos, const float* custom_table,

@@ -234,6 +234,30 @@ HCP_KERNEL(256) quick_gelu_kernel(const hcp_bf16* x, const hcp_bf16* dy, hcp_bf1
     }
 }
 
+// CLIP bigG / CLIPTextModelWithProjection MLP activation (hidden_act "gelu"): exact erf GELU on the Phi / phi helper the GEGLU kernels
+// use (hcp_device.h).  dy == null: y = x Phi(x); else dx = dy (Phi(x) + x phi(x)).  16-byte body, scalar tail of n % 8 elements.
+HCP_KERNEL(256) gelu_kernel(const hcp_bf16* x, const hcp_bf16* dy, hcp_bf16* out, long n) {
+    const long nvec = n / 8;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (long)gridDim.x * blockDim.x) {
+        hcp_bf16x8 v = *(const hcp_bf16x8*)(x + i * 8);
+        hcp_bf16x8 d = dy ? *(const hcp_bf16x8*)(dy + i * 8) : hcp_zero8();
+        hcp_bf16x8 o;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const float f = hcp_bf2f((unsigned short)v[q]);
+            o[q] = (short)hcp_f2bf(dy ? hcp_bf2f((unsigned short)d[q]) * gelu_erf_grad(f) : gelu_erf(f));
+        }
+        *(hcp_bf16x8*)(out + i * 8) = o;
+    }
+    if (blockIdx.x == 0) {
+        const long i = nvec * 8 + threadIdx.x;
+        if (threadIdx.x < 8 && i < n) {
+            const float f = hcp_bf2f(x[i]);
+            out[i] = hcp_f2bf(dy ? hcp_bf2f(dy[i]) * gelu_erf_grad(f) : gelu_erf(f));
+        }
+    }
+}
+
 // out[i, :] = tok[ids[i], :] + pos[pos_ids ? pos_ids[i] : i % L, :]   (CLIPTextEmbeddings, te_struct.txt; fp32 tables -> bf16 rows)
 HCP_KERNEL(256) embedding_kernel(const float* tok, const long long* ids, const float* pos, const long long* pos_ids, hcp_bf16* out,
                                  long n, int C, int L) {
@@ -466,6 +490,13 @@ HCP_API int hcp_quick_gelu(const void* x, const void* dy, void* out, long n, hip
     HCP_REQUIRE(x && out && n > 0 && n % 8 == 0, "hcp_quick_gelu: bad arguments");
     HCP_LAUNCH(quick_gelu_kernel, dim3(pw_grid(n / 8)), dim3(PW_THREADS), 0, stream, (const hcp_bf16*)x, (const hcp_bf16*)dy, (hcp_bf16*)out, n / 8);
     HCP_LAUNCH_CHECK("quick_gelu");
+}
+// y = gelu(x) (exact, dy == NULL) or dx = dy * gelu'(x); n bf16 elements (any n > 0), 16-byte aligned buffers
+HCP_API int hcp_gelu(const void* x, const void* dy, void* out, long n, hipStream_t stream) {
+    HCP_REQUIRE(x && out && n > 0, "hcp_gelu: bad arguments");
+    HCP_REQUIRE(((size_t)x | (size_t)dy | (size_t)out) % 16 == 0, "hcp_gelu: buffers must be 16-byte aligned");
+    HCP_LAUNCH(gelu_kernel, dim3(pw_grid(n / 8)), dim3(PW_THREADS), 0, stream, (const hcp_bf16*)x, (const hcp_bf16*)dy, (hcp_bf16*)out, n);
+    HCP_LAUNCH_CHECK("gelu");
 }
 // out[n, C] (bf16) = token_table[ids] + position_table[position_ids or (row % L)]; fp32 tables, int64 ids, C % 8 == 0
 HCP_API int hcp_embedding_bf16(const float* token_table, const long long* ids, const float* position_table, const long long* position_ids,

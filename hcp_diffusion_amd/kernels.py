@@ -637,6 +637,50 @@ def quick_gelu(x, dy=None):
     return out
 
 
+def gelu(x, dy=None):
+    """Exact (erf) GELU (dy None) or dy * gelu'(x); bf16, any shape and any numel > 0 (hidden_act "gelu" of CLIP bigG's MLP)."""
+    assert x.dtype == BF16 and x.is_contiguous() and (dy is None or (dy.dtype == BF16 and dy.is_contiguous() and dy.shape == x.shape))
+    out = torch.empty_like(x)
+    _chk(lib().hcp_gelu(_p(x), _p(dy), _p(out), x.numel(), _stream(x)), "hcp_gelu")
+    return out
+
+
+def _clip_pool_args(x, gamma, w):
+    assert x.dtype == BF16 and x.dim() == 3 and x.is_contiguous()
+    assert gamma.dtype == torch.float32 and gamma.is_contiguous() and gamma.numel() == x.shape[2]
+    assert w.dtype in (BF16, torch.float32) and w.dim() == 2 and w.is_contiguous() and w.shape[1] == x.shape[2]
+    return 1 if w.dtype == torch.float32 else 0
+
+
+def clip_pool_fwd(x, ids, gamma, beta, w, repeats=1, eps=1e-5):
+    """x bf16 [B*r, L, C] (last hidden states), ids int64 [B*r, L], final_layer_norm gamma / beta fp32 [C], w = text_projection.weight
+    [P, C] (bf16 or fp32) -> (pooled fp32 [B, P], positions int32 [B*r], stats fp32 [B*r, 2]): the r chunks' projections averaged."""
+    w_f32 = _clip_pool_args(x, gamma, w)
+    M, L, C = x.shape
+    assert ids.dtype == torch.int64 and ids.is_contiguous() and tuple(ids.shape) == (M, L) and M % repeats == 0
+    assert beta.dtype == torch.float32 and beta.is_contiguous() and beta.numel() == C
+    B, P = M // repeats, w.shape[0]
+    pooled = torch.empty((B, P), dtype=torch.float32, device=x.device)
+    pos = torch.empty((M,), dtype=torch.int32, device=x.device)
+    stats = torch.empty((M, 2), dtype=torch.float32, device=x.device)
+    _chk(lib().hcp_clip_pool_fwd(_p(x), _p(ids), _p(gamma), _p(beta), _p(w), w_f32, _p(pooled), _p(pos), _p(stats), B, repeats, L, C, P,
+                                 float(eps), _stream(x)), "hcp_clip_pool_fwd")
+    return pooled, pos, stats
+
+
+def clip_pool_bwd(x, pos, stats, gamma, w, d_pooled, repeats=1):
+    """d_pooled fp32 [B, P] -> dx bf16 [B*r, L, C]: zero except each row's EOS token (a fresh tensor, written by the kernel)."""
+    w_f32 = _clip_pool_args(x, gamma, w)
+    M, L, C = x.shape
+    B, P = M // repeats, w.shape[0]
+    assert d_pooled.dtype == torch.float32 and d_pooled.is_contiguous() and tuple(d_pooled.shape) == (B, P)
+    assert pos.dtype == torch.int32 and pos.numel() == M and stats.dtype == torch.float32 and stats.numel() == 2 * M
+    dx = torch.empty_like(x)
+    _chk(lib().hcp_clip_pool_bwd(_p(x), _p(pos), _p(stats), _p(gamma), _p(w), w_f32, _p(d_pooled), _p(dx), B, repeats, L, C, P, _stream(x)),
+         "hcp_clip_pool_bwd")
+    return dx
+
+
 def embedding(token_table, ids, position_table, position_ids=None):
     """[.., L] int64 ids -> bf16 [.., L, C] = token_table[ids] + position_table[position_ids or arange(L)]."""
     assert token_table.dtype == torch.float32 and position_table.dtype == torch.float32 and token_table.is_contiguous() and position_table.is_contiguous()

@@ -611,6 +611,47 @@ def quick_gelu(x):
     return _QuickGeluFn.apply(x)
 
 
+class _GeluFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return K.gelu(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return K.gelu(x, dy.contiguous())
+
+
+def gelu(x):
+    return _GeluFn.apply(x)
+
+
+class _ClipPoolFn(torch.autograd.Function):
+    """text_projection(final_layer_norm(x)[eos]) averaged over the prompt's chunks (kernels.clip_pool_fwd / _bwd).  The norm's affine
+    and the projection are constants: the only gradient is the one into the last hidden states."""
+
+    @staticmethod
+    def forward(ctx, x, ids, gamma, beta, w, repeats, eps):
+        pooled, pos, stats = K.clip_pool_fwd(x, ids, gamma, beta, w, repeats, eps)
+        ctx.save_for_backward(x, pos, stats, gamma, w)
+        ctx.repeats = repeats
+        ctx.mark_non_differentiable(pos)
+        return pooled, pos
+
+    @staticmethod
+    def backward(ctx, d_pooled, _d_pos):
+        x, pos, stats, gamma, w = ctx.saved_tensors
+        dx = K.clip_pool_bwd(x, pos, stats, gamma, w, d_pooled.float().contiguous(), ctx.repeats)
+        return dx, None, None, None, None, None, None
+
+
+def clip_pool(x, ids, ln, w, repeats=1):
+    """(pooled fp32 [B, P], eos positions int32 [B*r]) from the last hidden states x bf16 [B*r, L, C]; ln = final_layer_norm, w =
+    text_projection.weight (bf16 or fp32), both frozen."""
+    return _ClipPoolFn.apply(x, ids, ln.weight.detach(), ln.bias.detach(), w, repeats, float(ln.eps))
+
+
 class _AttentionPackedFn(torch.autograd.Function):
     """Attention on fused projection buffers: `a` = [B,N,3C] (q|k|v, self-attention) or `a` = q [B,N,C] with
     `kv` = [B,Nk,2C] (k|v, cross-attention).  The kernels read the column slices in place and write the gradients

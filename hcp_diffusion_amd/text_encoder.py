@@ -14,6 +14,10 @@ Kernels: ``hcp_embedding_bf16`` (or, with a prompt-tuning ``emb_ex`` hook on ``t
 ``hcp_quick_gelu``.  Output selection follows ``TEEXHook.forward_hook`` (textencoder_ex.py:62-79) for N_repeats = 1:
 ``final_layer_norm(hidden_states[-clip_skip-1])``; ``N_repeats`` > 1 (``tokenizer_repeats``) encodes [B, r x 77] ids as B r prompts and stitches
 the chunks back with one BOS and one EOS, as the hook does.
+
+SDXL: ``hidden_act="gelu"`` (``hcp_gelu``) and ``projection_dim`` (``text_projection.weight``; the pooled output
+``text_projection(final_layer_norm(last)[eos])`` from ``hcp_clip_pool_fwd`` / ``_bwd``) make the same class bigG's
+``CLIPTextModelWithProjection``; ``NativeSDXLTextEncoder`` composes ``clip_B`` and ``clip_bigG`` like the reference's ``ComposeTextEncoder``.
 """
 import json
 import os
@@ -28,6 +32,11 @@ from .layers import HipLayerNorm, HipLinear
 BF16 = torch.bfloat16
 CLIP_L_CONFIG = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12,
                      max_position_embeddings=77)
+
+
+# what bigG (CLIPTextModelWithProjection, SDXL's text_encoder_2) adds over CLIP-L: the MLP activation and the pooled projection
+_XL_DEFAULTS = dict(hidden_act="quick_gelu", projection_dim=None)
+CONFIG_KEYS = tuple(CLIP_L_CONFIG) + tuple(_XL_DEFAULTS)
 
 
 class _Config(dict):
@@ -49,21 +58,25 @@ class CLIPAttention(nn.Module):
         return _call(self.out_proj, ops.attention(q, k, v, self.heads, key_bias=key_bias, causal=True), residual)
 
 
+_ACTS = {"quick_gelu": ops.quick_gelu, "gelu": ops.gelu}          # CLIP-L / clip_B: quick_gelu; bigG: exact erf GELU (config.json hidden_act)
+
+
 class CLIPMLP(nn.Module):
-    def __init__(self, c, inner):
+    def __init__(self, c, inner, act="quick_gelu"):
         super().__init__()
         self.fc1 = HipLinear(c, inner); self.fc2 = HipLinear(inner, c)
+        self.act = _ACTS[act]
 
     def forward(self, x, residual):
-        return _call(self.fc2, ops.quick_gelu(self.fc1(x)), residual)
+        return _call(self.fc2, self.act(self.fc1(x)), residual)
 
 
 class CLIPEncoderLayer(nn.Module):
-    def __init__(self, c, heads, inner):
+    def __init__(self, c, heads, inner, act="quick_gelu"):
         super().__init__()
         self.self_attn = CLIPAttention(c, heads)
         self.layer_norm1 = HipLayerNorm(c, eps=1e-5)
-        self.mlp = CLIPMLP(c, inner)
+        self.mlp = CLIPMLP(c, inner, act)
         self.layer_norm2 = HipLayerNorm(c, eps=1e-5)
 
     def forward(self, x, key_bias=None):
@@ -81,27 +94,31 @@ class _Embeddings(nn.Module):
 
 
 class _Encoder(nn.Module):
-    def __init__(self, c, heads, inner, n):
+    def __init__(self, c, heads, inner, n, act="quick_gelu"):
         super().__init__()
-        self.layers = nn.ModuleList([CLIPEncoderLayer(c, heads, inner) for _ in range(n)])
+        self.layers = nn.ModuleList([CLIPEncoderLayer(c, heads, inner, act) for _ in range(n)])
 
 
 class _TextTransformer(nn.Module):
-    def __init__(self, vocab_size, hidden_size, intermediate_size, num_hidden_layers, num_attention_heads, max_position_embeddings):
+    def __init__(self, vocab_size, hidden_size, intermediate_size, num_hidden_layers, num_attention_heads, max_position_embeddings,
+                 hidden_act="quick_gelu"):
         super().__init__()
         self.embeddings = _Embeddings(vocab_size, hidden_size, max_position_embeddings)
-        self.encoder = _Encoder(hidden_size, num_attention_heads, intermediate_size, num_hidden_layers)
+        self.encoder = _Encoder(hidden_size, num_attention_heads, intermediate_size, num_hidden_layers, hidden_act)
         self.final_layer_norm = HipLayerNorm(hidden_size, eps=1e-5)
 
 
 class NativeCLIPTextModel(nn.Module):
     def __init__(self, clip_skip=0, clip_final_norm=True, N_repeats=1, **cfg):
         super().__init__()
-        keys = tuple(CLIP_L_CONFIG)
-        self.config = _Config({**CLIP_L_CONFIG, **{k: v for k, v in cfg.items() if k in keys}})
+        self.config = _Config({**CLIP_L_CONFIG, **_XL_DEFAULTS, **{k: v for k, v in cfg.items() if k in CONFIG_KEYS}})
+        if self.config["hidden_act"] not in _ACTS:
+            raise NotImplementedError(f"hcp_diffusion_amd: text-encoder hidden_act={self.config['hidden_act']!r} (quick_gelu or gelu)")
         if self.config["hidden_size"] // self.config["num_attention_heads"] not in (40, 64, 80, 160):
             raise NotImplementedError("hcp_diffusion_amd: text-encoder head width must be one of 40/64/80/160")
-        self.text_model = _TextTransformer(**self.config)
+        self.text_model = _TextTransformer(**{k: v for k, v in self.config.items() if k != "projection_dim"})
+        if self.config["projection_dim"] is not None:         # CLIPTextModelWithProjection: same names, plus text_projection.weight
+            self.text_projection = nn.Linear(self.config["hidden_size"], self.config["projection_dim"], bias=False)
         self.clip_skip, self.clip_final_norm, self.N_repeats = clip_skip, clip_final_norm, N_repeats
 
     @property
@@ -120,6 +137,7 @@ class NativeCLIPTextModel(nn.Module):
         (text-encoder LoRA training, lora_conventional.yaml:14-19) replay captured hipGraphs, one pair per input signature."""
         self._hip_graph, self._hip_graphs = bool(on), {}
         self._hcp_capturable = None
+        self.pack_projection()
 
     def forward(self, input_ids, position_ids=None, attention_mask=None, output_hidden_states=None):
         if (getattr(self, "_hip_graph", False) and torch.is_grad_enabled() and input_ids.is_cuda
@@ -129,7 +147,10 @@ class NativeCLIPTextModel(nn.Module):
             # steps, like the per-step forward hooks capturable() refuses), and the custom vectors' gradient leaves through autograd or
             # the trainer's sink, not through the LoRA / host buckets the captured backward writes.  (NativeTrainer(use_graph=True)
             # captures the whole step, the prompt-tuning kernels included.)
-            if getattr(self.text_model.embeddings.token_embedding, "emb_ex", None) is None and graphed.capturable_cached(self)[0]:
+            # With projection_dim the forward has two outputs (states, pooled) and stays eager as well: graphed.call replays one output
+            # tensor and its gradient.  (NativeTrainer(use_graph=True) captures the whole step, both outputs included.)
+            if (getattr(self.text_model.embeddings.token_embedding, "emb_ex", None) is None and self.config["projection_dim"] is None
+                    and graphed.capturable_cached(self)[0]):
                 ins = [input_ids, position_ids, attention_mask]
                 key = tuple(None if t is None else (tuple(t.shape), t.dtype) for t in ins)
                 x = graphed.call(self, ins, lambda i_, p_, m_: self._forward_impl(i_, p_, m_), self._hip_graphs, key)
@@ -174,13 +195,55 @@ class NativeCLIPTextModel(nn.Module):
         if attention_mask is not None:       # [B, L], 1 = attend (wrapper.py:20 passes the tokenizer's mask when encoder_attention_mask is on)
             key_bias = ((1.0 - attention_mask.to(torch.float32)) * -1.0e9).contiguous()       # additive on the keys, on top of the causal mask
         layers = tm.encoder.layers
-        for layer in layers[:len(layers) - self.clip_skip]:
+        proj = self.config["projection_dim"] is not None
+        if proj and torch.is_grad_enabled() and (self.text_projection.weight.requires_grad or tm.final_layer_norm.weight.requires_grad
+                                                 or tm.final_layer_norm.bias.requires_grad):
+            raise NotImplementedError("hcp_diffusion_amd: final_layer_norm and text_projection are frozen on the pooled-output path")
+        n_states = len(layers) - self.clip_skip               # the states are hidden_states[-clip_skip-1] = the output of this many layers
+        sel = x
+        for i, layer in enumerate(layers[:len(layers) if proj else n_states]):        # the pooled output needs the last layer
             x = layer(x, key_bias)
-        x = tm.final_layer_norm(x) if self.clip_final_norm else x
+            if i < n_states:
+                sel = x
+        if proj:      # text_embeds = text_projection(final_layer_norm(last)[eos]), mean over the r chunks (textencoder_ex.py:73-76)
+            pooled, _ = ops.clip_pool(x, input_ids.contiguous(), tm.final_layer_norm, self._projection_weight(), r)
+        x = tm.final_layer_norm(sel) if self.clip_final_norm else sel
         if r > 1:       # textencoder_ex.py:68-72: one BOS (first chunk), every chunk's inner tokens, one EOS (last chunk) -> [B, r*(L-2)+2, C]
             x = x.reshape(B, r, *x.shape[1:])
             x = torch.cat([x[:, 0, :1, :], x[:, :, 1:-1, :].flatten(1, 2), x[:, -1, -1:, :]], dim=1)
+        if proj:
+            return x, pooled
         return (x, None) if output_hidden_states is not None else x
+
+    def pack_projection(self):
+        """The bf16 copy of text_projection.weight the pooling kernel reads.  Made here — after load_state_dict, a device / dtype move
+        (``_apply``) and enable_hip_graph() — so that a graph capture finds it ready."""
+        if self.config["projection_dim"] is not None and not self.text_projection.weight.is_meta:
+            w = self.text_projection.weight
+            self._proj_bf16 = ((w._version, w.data_ptr(), w.device), w.detach().to(BF16).contiguous())
+
+    def load_state_dict(self, *args, **kwargs):
+        out = super().load_state_dict(*args, **kwargs)
+        self.pack_projection()
+        return out
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self.pack_projection()
+        return out
+
+    def _projection_weight(self):
+        """The packed copy; re-made when the weight was written in place since.  Never cached from inside a capture: a tensor allocated
+        there lives in the graph's pool and is filled only on replay, so that call converts in the graph instead and keeps nothing."""
+        w = self.text_projection.weight
+        key = (w._version, w.data_ptr(), w.device)
+        hit = getattr(self, "_proj_bf16", None)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        if w.is_cuda and torch.cuda.is_current_stream_capturing():
+            return w.detach().to(BF16).contiguous()
+        self.pack_projection()
+        return self._proj_bf16[1]
 
     @classmethod
     def from_pretrained(cls, path=None, subfolder="text_encoder", device="cuda", pretrained_model_name_or_path=None, hip_graph=False, **kw):
@@ -189,8 +252,10 @@ class NativeCLIPTextModel(nn.Module):
         path = path if path is not None else pretrained_model_name_or_path
         root = os.path.join(path, subfolder) if subfolder and os.path.isdir(os.path.join(path, subfolder)) else path
         cfg = json.load(open(os.path.join(root, "config.json")))
-        model = cls(**kw, **{k: cfg[k] for k in CLIP_L_CONFIG if k in cfg})
         sd = load_file(os.path.join(root, "model.safetensors"))
+        if "text_projection.weight" not in sd:            # a plain CLIPTextModel's config.json carries projection_dim too: no pooled head
+            cfg = {k: v for k, v in cfg.items() if k != "projection_dim"}
+        model = cls(**kw, **{k: cfg[k] for k in CONFIG_KEYS if k in cfg})
         own = model.state_dict()
         sd = {k: v for k, v in sd.items() if k in own}                   # position_ids buffer etc. are ignored
         missing = [k for k in own if k not in sd]
@@ -201,3 +266,57 @@ class NativeCLIPTextModel(nn.Module):
         if hip_graph:
             model.enable_hip_graph()
         return model
+
+
+class NativeSDXLTextEncoder(nn.Module):
+    """SDXL's text path: the reference's ``ComposeTextEncoder([('clip_B', ...), ('clip_bigG', ...)])`` with a ``TEEXHook`` on each encoder
+    (hcpdiff/models/compose/compose_textencoder.py:75-91), on two native encoders.  The children keep the reference's names, so the
+    ``re:.*self_attn$`` / ``re:.*mlp$`` selectors of cfgs/train/examples/lora_sdxl.yaml, ``re:clip_bigG.*mlp$``, checkpoints
+    (``clip_B.text_model...`` / ``clip_bigG.text_model...`` / ``clip_bigG.text_projection.weight``) and lora_convert's ``lora_te1_`` /
+    ``lora_te2_`` keys line up.  ``forward`` answers with the hooked pair's tuple ``(states [B, L, C_B + C_bigG], [pooled_B, pooled_bigG])``
+    — ``pooled_B`` is None (a plain CLIPTextModel host: no projection) — of which SDXLTEUnetWrapper (models/wrapper.py:57-74) feeds
+    ``pooled[-1]`` to the UNet as ``text_embeds``."""
+
+    def __init__(self, clip_B, clip_bigG):
+        super().__init__()
+        if clip_bigG.config["projection_dim"] is None:
+            raise ValueError("NativeSDXLTextEncoder: clip_bigG must be built with projection_dim (CLIPTextModelWithProjection)")
+        self.clip_B, self.clip_bigG = clip_B, clip_bigG
+        self.model_names = ["clip_B", "clip_bigG"]
+
+    @property
+    def device(self):
+        return self.clip_bigG.device
+
+    @property
+    def dtype(self):
+        return self.clip_bigG.dtype
+
+    def get_input_embeddings(self):
+        return [getattr(self, name).get_input_embeddings() for name in self.model_names]
+
+    def enable_hip_graph(self, on=True):
+        """Forwarded to the children: clip_B replays captured graphs; clip_bigG (two outputs) stays eager (NativeCLIPTextModel.forward)."""
+        for name in self.model_names:
+            getattr(self, name).enable_hip_graph(on)
+
+    def forward(self, input_ids, attention_mask=None, position_ids=None, output_hidden_states=None):
+        """int64 [B, 2 x L] ids (clip_B's tokens | clip_bigG's tokens; L = r x 77 with N_repeats = r) -> (bf16 [B, L', C_B + C_bigG], [None, fp32 [B, P]])."""
+        if input_ids.shape[-1] % 2:
+            raise ValueError(f"token ids [B, 2 x L] expected (one half per encoder), got {tuple(input_ids.shape)}")
+        states, pooled = [], []
+        for name, ids in zip(self.model_names, input_ids.chunk(2, dim=-1)):
+            s, p = getattr(self, name)(ids.contiguous(), position_ids=position_ids, attention_mask=attention_mask, output_hidden_states=True)
+            states.append(s); pooled.append(p)
+        return ops.concat_channels(states[0].contiguous(), states[1].contiguous()), pooled
+
+    @classmethod
+    def from_pretrained(cls, path=None, device="cuda", pretrained_model_name_or_path=None, hip_graph=False, **kw):
+        """A diffusers SDXL directory: ``text_encoder/`` -> clip_B, ``text_encoder_2/`` -> clip_bigG.  kw (clip_skip, clip_final_norm,
+        N_repeats) goes to both encoders, as the reference hooks both with one setting."""
+        path = path if path is not None else pretrained_model_name_or_path
+        pair = cls(NativeCLIPTextModel.from_pretrained(path, subfolder="text_encoder", device=device, **kw),
+                   NativeCLIPTextModel.from_pretrained(path, subfolder="text_encoder_2", device=device, **kw))
+        if hip_graph:
+            pair.enable_hip_graph()
+        return pair

@@ -301,6 +301,11 @@ class NativeTrainer:
                     raise ValueError("a batch needs encoder_hidden_states, or prompt_ids together with a text_encoder")
                 with torch.set_grad_enabled(self.te_bucket is not None or getattr(self, "pt_bucket", None) is not None):
                     encoder_hidden_states = self.text_encoder(prompt_ids, attention_mask=attn_mask)
+                if isinstance(encoder_hidden_states, tuple):              # the SDXL pair answers (states, [pooled_B, pooled_bigG]):
+                    encoder_hidden_states, pooled = encoder_hidden_states  # wrapper.py:64-73 feeds pooled[-1] with the batch's crop_info
+                    if not added_cond_kwargs or added_cond_kwargs.get("time_ids") is None:
+                        raise ValueError("an SDXL text encoder needs the batch's added_cond_kwargs={'time_ids': ...}")
+                    added_cond_kwargs = dict(added_cond_kwargs, text_embeds=pooled[-1])
             if plugin_input:                                              # wrapper.py:15,25-28: feeders see the batch dict
                 for feeder in getattr(self.unet, "input_feeder", []):
                     feeder(dict(noisy_latents=noisy, timesteps=t, encoder_hidden_states=encoder_hidden_states, **plugin_input))

@@ -30,8 +30,9 @@ int hcp_is_emulated(void); /* 0 for the product library */
  * (ldt on hcp_gemm_lora_bf16 / hcp_gemm_geglu_bwd_bf16, l_lo, ldu / ldt) are covered by the same bump.  3: round 6 — the (hi | lo)
  * residual stream: residual_lo / D_lo on hcp_gemm_bf16 / hcp_gemm_lora_bf16, x_lo / addend_lo / dx_lo on hcp_layernorm_fwd / _bwd; the
  * GEGLU-forward output gact on hcp_gemm_bf16 / hcp_gemm_lora_bf16.  4: prompt tuning — hcp_embedding_pt_fwd_bf16 /
- * hcp_embedding_pt_bwd_f32 (csrc/embedding.hip).  5: folded upsampler convs — hcp_conv_fold_pack / hcp_conv3x3_up_fold_bf16. */
-#define HCP_ABI_VERSION 5
+ * hcp_embedding_pt_bwd_f32 (csrc/embedding.hip).  5: folded upsampler convs — hcp_conv_fold_pack / hcp_conv3x3_up_fold_bf16.
+ * 6: SDXL's second text encoder — hcp_gelu, hcp_clip_pool_fwd / hcp_clip_pool_bwd. */
+#define HCP_ABI_VERSION 6
 int hcp_abi_version(void);
 /* Device self-check of the fp32 atomic path (no reference counterpart: the reference's sums are torch's).  workgroups x 256 threads add
  * small integers into line[16] and into bucket[i * stride], i < nb (both cleared here first); exact expected values:
@@ -211,6 +212,22 @@ int hcp_embedding_pt_fwd_bf16(const long long* ids, int B, int R, int W, int n_w
 /* grad[k, :] (beta 1: +)= sum over the M rows m with src_map[m] == -1 - k of dX[m, :] (bf16 [M, C]), summed in increasing m by one
  * workgroup per (k, 256-column slab): no atomics, bit-reproducible.  grad fp32 [n_custom, C]. */
 int hcp_embedding_pt_bwd_f32(const void* dX, const int* src_map, long M, int C, float* grad, int n_custom, int beta, hcpStream_t stream);
+/* SDXL's second text encoder (CLIPTextModelWithProjection, "clip_bigG"; cfgs/train/examples/lora_sdxl.yaml trains LoRA on it).
+ * hcp_gelu: its MLP activation (hidden_act "gelu": exact erf GELU), same calling shape as hcp_quick_gelu; any n > 0 (16-byte body,
+ * scalar tail), 16-byte aligned buffers. */
+int hcp_gelu(const void* x, const void* dy, void* out, long n, hcpStream_t stream);   /* dy NULL: forward; else dx */
+/* Pooled output: pooled[b, :] = mean over the R chunks k of text_projection(final_layer_norm(x[b*R + k, eos, :])) (TEEXHook.forward_hook,
+ * hcpdiff/models/textencoder_ex.py:73-76), eos = the FIRST position of the row's maximum id (transformers' rule for eos_token_id == 2).
+ * x bf16 [B*R, L, C] (last layer's hidden states), ids int64 [B*R, L], gamma / beta fp32 [C], W = text_projection.weight [P, C]
+ * (bf16, or fp32 with w_is_f32), pooled fp32 [B, P]; also written: positions int32 [B*R] and stats fp32 [B*R, 2] = (mean, rstd) of
+ * the chosen token, which the backward reads.  One workgroup per (prompt, 16 output columns); no atomics.  C % 8 == 0, C <= 8192. */
+int hcp_clip_pool_fwd(const void* x, const long long* ids, const float* gamma, const float* beta, const void* W, int w_is_f32,
+                      float* pooled, int* positions, float* stats, int B, int R, int L, int C, int P, float eps, hcpStream_t stream);
+/* dx bf16 [B*R, L, C] is WRITTEN (not added to): zero everywhere except row positions[m] of each m, which holds the LayerNorm
+ * backward of W^T d_pooled[m / R] / R.  gamma and W are constants here (no gradient for final_layer_norm / text_projection).
+ * One workgroup per row m, column sums in a fixed order: bit-reproducible.  C % 8 == 0, C + P <= 8192. */
+int hcp_clip_pool_bwd(const void* x, const int* positions, const float* stats, const float* gamma, const void* W, int w_is_f32,
+                      const float* d_pooled, void* dx, int B, int R, int L, int C, int P, hcpStream_t stream);
 /* per-sample loss weights of the reference's timestep-aware criteria (hcpdiff/loss/min_snr_loss.py): kind 0 MinSNRLoss :21-25,
  * 1 SoftMinSNRLoss :31-35, 2 KDiffMinSNRLoss :39-43, 3 EDMLoss :47-52; snr = acp/(1-acp) as in :14-19.  w: float[B]. */
 int hcp_snr_loss_weight(const long long* timesteps, const float* alphas_cumprod, float* w, int B, int kind, float gamma,
