@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 import attn_check as AC
 import gemm_check as GC
+import norm_check as NC
 from hcp_diffusion_amd import kernels as K
 
 BF = torch.bfloat16
@@ -478,6 +479,10 @@ def test_groupnorm_silu(backend, case):
     skip = rnd(B, C, H, W)                                   # fused residual-path gradient
     dx2 = K.groupnorm_bwd(to(nhwc(x)), to(nhwc(dy)), to(gamma), to(beta), stats, 32, silu, addend=to(nhwc(skip)))
     assert relerr(dx2.permute(0, 3, 1, 2), xr.grad + skip.float()) < 1e-2
+    for kind, addend in (("gn_bwd", False), ("gn_bwd", True), ("gn_affine", False)):       # the same shape element-wise against float64
+        d = NC.desc(kind, B=B, HW=H * W, C=C, G=32, silu=silu, eps=eps, addend=addend)
+        ops = NC.make_operands(d, backend.device)
+        NC.check(d, ops, NC.run(d, ops))
 
 
 @pytest.mark.parametrize("B,H,W,C,silu", [(2, 3, 5, 640, True), (1, 4, 4, 2560, False), (2, 3, 5, 320, True), (4, 16, 16, 1280, True),
@@ -509,10 +514,28 @@ def test_groupnorm_slab_path_matches_row_chunk_path(tbackend, B, H, W, C, silu):
     yr = F.silu(yr) if silu else yr
     yr.backward(dy.float().permute(0, 3, 1, 2))
     assert relerr(y1.permute(0, 3, 1, 2), yr) < 1e-2 and relerr(d1.permute(0, 3, 1, 2), xr.grad + skip.float().permute(0, 3, 1, 2)) < 1e-2
+    for slab in (False, True):                               # both paths element-wise against float64 (norm_check sets and restores the hook)
+        d = NC.desc("gn_bwd", B=B, HW=H * W, C=C, G=32, silu=silu, addend=True, slab=slab)
+        ops = NC.make_operands(d, tbackend.device)
+        NC.check(d, ops, NC.run(d, ops))
 
 
 @pytest.mark.parametrize("B,H,W,C", [(1, 10, 10, 320), (2, 12, 14, 1280), (4, 64, 64, 320), (2, 128, 128, 320), (4, 32, 32, 1920)])
 def test_groupnorm_statistics_many_chunks_large_mean(backend, B, H, W, C):
+    _groupnorm_statistics_large_mean(backend, B, H, W, C)
+
+
+@pytest.mark.parametrize("B,H,W,C", [(1, 10, 10, 320), (2, 12, 14, 1280), (4, 64, 64, 320), (2, 128, 128, 320), (4, 32, 32, 1920)])
+def test_groupnorm_statistics_many_chunks_large_mean_row_chunk_path(tbackend, B, H, W, C):
+    """the same with the slab path off: on the default dispatch every shape but 128x128 runs the slab kernels and never reaches the merge."""
+    try:
+        K.lib().hcp_debug_set_gn_target(-1)
+        _groupnorm_statistics_large_mean(tbackend, B, H, W, C)
+    finally:
+        K.lib().hcp_debug_set_gn_target(-2)
+
+
+def _groupnorm_statistics_large_mean(backend, B, H, W, C):
     """The per-sample merge of chunk partials (shifted-sum form of Chan's formula, csrc/norm.hip gn_merge): ragged last chunk,
     more chunks than one merge round (12x14 @ C=1280: 42 chunks, 5 merge threads per group), |mean| >> std (offsets up to 60
     standard deviations, different per group).  (mean, rstd) vs an fp64 reference to 2e-4 relative."""
@@ -555,6 +578,10 @@ def test_layernorm(backend, M, C):
     assert relerr(dx, xr.grad) < 1e-2
     skip = rnd(M, C)
     assert relerr(K.layernorm_bwd(to(x), to(dy), to(gamma), stats, addend=to(skip)), xr.grad + skip.float()) < 1e-2
+    for kind, addend in (("ln_bwd", False), ("ln_bwd", True), ("ln_affine", False)):       # the same shape element-wise against float64
+        d = NC.desc(kind, M=M, C=C, addend=addend)
+        ops = NC.make_operands(d, backend.device)
+        NC.check(d, ops, NC.run(d, ops))
 
 
 @pytest.mark.parametrize("kind", ["group", "layer"])
@@ -1388,6 +1415,10 @@ def test_hi_lo_residual_stream_layernorm(backend, M, C):
     assert relerr(dx.float() + dx_lo.float(), want) < 1e-4
     one = K.layernorm_bwd(to(hi), to(dy), to(gamma), stats, addend=to(shi), x_lo=to(lo), addend_lo=to(slo))       # the stream's first norm: one bf16 gradient
     assert torch.equal(one.cpu(), dx.cpu())
+    for want_lo in (True, False):                            # the same shape element-wise against float64
+        d = NC.desc("ln_bwd", M=M, C=C, x_lo=True, addend=True, addend_lo=True, want_lo=want_lo)
+        ops = NC.make_operands(d, backend.device)
+        NC.check(d, ops, NC.run(d, ops))
 
 
 def _geglu_bwd_ref(dff, hg, Fd):
