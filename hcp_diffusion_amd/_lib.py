@@ -7,7 +7,7 @@ The product path opens exactly one file — ``hcp_diffusion_amd/libhcp_mi355x.so
 """
 import ctypes
 import os
-from ctypes import c_int, c_long, c_float, c_void_p, c_size_t, c_char_p
+from ctypes import c_int, c_long, c_float, c_double, c_void_p, c_size_t, c_char_p
 from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "libhcp_mi355x.so"
@@ -111,6 +111,14 @@ _PROTOTYPES = {
     "hcp_sumsq_f32": (I, [P, L, P, P]),
     # p, g, m, v, n, lr, beta1, beta2, eps, wd, sumsq, grad_scale, max_norm, step, stream
     "hcp_adamw_clip_fused": (I, [P, P, P, P, L, P, F, F, F, F, P, F, F, P, P]),
+    # g, n, out, partials (2048 floats), stream
+    "hcp_sumsq_ordered_f32": (I, [P, L, P, P, P]),
+    # p, g, m, n, lr, beta1, beta2, wd, sumsq, grad_scale, max_norm, step, stream
+    "hcp_lion_clip_fused": (I, [P, P, P, L, P, c_double, c_double, F, P, F, F, P, P]),
+    "hcp_adafactor_desc_bytes": (I, []),
+    # p, g, m, row, col, full, descs, count, total_items, total_fitems, workspace, workspace_bytes, tstat, scal, lr, eps1, eps2,
+    # clip_threshold, decay_rate, beta1, wd, scale_parameter, relative_step, warmup_init, sumsq, grad_scale, max_norm, step, stream
+    "hcp_adafactor_step": (I, [P, P, P, P, P, P, P, I, I, I, P, c_size_t, P, P, P, F, F, F, F, c_double, F, I, I, I, P, F, F, P, P]),
     # data-parallel exchange (RCCL, csrc/comm.hip)
     "hcp_comm_unique_id": (I, [P]),
     "hcp_comm_init": (I, [I, I, P, ctypes.POINTER(P)]),

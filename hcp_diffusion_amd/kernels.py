@@ -6,6 +6,8 @@ kernel on torch's *current* stream.  Nothing here computes with torch ops.
 import ctypes
 import math
 import os
+
+import numpy as np
 import torch
 
 from . import _lib
@@ -889,6 +891,16 @@ def sumsq(g, out):
     return out
 
 
+SUMSQ_PARTIALS = 2048          # include/hcp_mi355x.h HCP_SUMSQ_PARTIALS
+
+
+def sumsq_ordered(g, out, partials):
+    """sumsq without atomics (block partials added in a fixed order): the same bits on every run."""
+    assert g.dtype == torch.float32 and g.is_contiguous() and partials.dtype == torch.float32 and partials.numel() >= SUMSQ_PARTIALS
+    _chk(lib().hcp_sumsq_ordered_f32(_p(g), g.numel(), _p(out), _p(partials), _stream(g)), "hcp_sumsq_ordered_f32")
+    return out
+
+
 def adamw_clip_fused(p, g, m, v, lr, step, *, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2, sumsq_t=None,
                      grad_scale=1.0, max_norm=0.0):
     for t in (p, g, m, v):
@@ -896,6 +908,119 @@ def adamw_clip_fused(p, g, m, v, lr, step, *, beta1=0.9, beta2=0.999, eps=1e-8, 
     assert lr.dtype == torch.float32 and step.dtype == torch.int32
     _chk(lib().hcp_adamw_clip_fused(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(lr), beta1, beta2, eps, weight_decay,
                                     _p(sumsq_t), float(grad_scale), float(max_norm), _p(step), _stream(p)), "hcp_adamw_clip_fused")
+
+
+def lion_clip_fused(p, g, m, lr, step, *, beta1=0.9, beta2=0.99, weight_decay=0.0, sumsq_t=None, grad_scale=1.0, max_norm=0.0):
+    """lion_pytorch.Lion on a flat bucket (csrc/optim_factored.hip), calling conventions of adamw_clip_fused."""
+    for t in (p, g, m):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel()
+    assert lr.dtype == torch.float32 and step.dtype == torch.int32
+    _chk(lib().hcp_lion_clip_fused(_p(p), _p(g), _p(m), p.numel(), _p(lr), beta1, beta2, weight_decay, _p(sumsq_t), float(grad_scale),
+                                   float(max_norm), _p(step), _stream(p)), "hcp_lion_clip_fused")
+
+
+AF_DESC_DTYPE = np.dtype([("off", "<i8"), ("row_off", "<i8"), ("col_off", "<i8"), ("full_off", "<i8"), ("rowp_off", "<i8"), ("colp_off", "<i8"),
+                          ("s_outer", "<i8"), ("s_inner", "<i8"), ("s_r", "<i8"), ("s_c", "<i8"), ("kind", "<i4"), ("outer", "<i4"),
+                          ("inner", "<i4"), ("R", "<i4"), ("C", "<i4"), ("item0", "<i4"), ("fitem0", "<i4"), ("pad", "<i4")])
+AF_VEC, AF_MAT, AF_TILE = 0, 1, 2
+_AF_TR, _AF_TC, _AF_VEC_ITEM = 32, 1024, 4096           # csrc/optim_factored.hip: MAT tile, VEC elements per work item
+
+
+class AdafactorTable:
+    """Descriptor table + state of hcp_adafactor_step for the tensors of one flat bucket (or of one lr segment of it).
+
+    tensors: [(name, offset in the bucket, logical shape, element strides)].  Three kinds (anything else raises with the name):
+    VEC 1-D unfactored; MAT 2-D row-major; TILE 4-D [O, I, kh, kw] with kh, kw <= 3, any dense layout (the buckets keep 3x3 weights
+    channels_last, an optimizer over plain parameters sees them contiguous).  State lives in three flat buffers with the installed
+    class's per-tensor shapes: row [.., R] and col [.., C] second moments, `full` for VEC; `views(i)` cuts tensor i's out."""
+
+    def __init__(self, tensors, device):
+        rows, self.meta = [], []
+        item0 = fitem0 = nrow = ncol = nfull = nws = 0
+        pad4 = lambda n: (n + 3) // 4 * 4
+        for name, off, shape, stride in tensors:
+            shape, stride = tuple(int(s) for s in shape), tuple(int(s) for s in stride)
+            n = int(np.prod(shape)) if shape else 1
+            if n == 0:
+                raise ValueError(f"Adafactor: parameter {name!r} is empty")
+            r = dict(off=off, row_off=0, col_off=0, full_off=0, rowp_off=0, colp_off=0, s_outer=0, s_inner=0, s_r=0, s_c=1,
+                     outer=1, inner=1, R=1, C=n, item0=item0, fitem0=fitem0, pad=0)
+            if len(shape) <= 1:
+                if len(shape) == 1 and n > 1 and stride != (1,):
+                    raise ValueError(f"Adafactor: 1-D parameter {name!r} is not contiguous")
+                r.update(kind=AF_VEC, full_off=nfull)
+                items, fitems = -(-n // _AF_VEC_ITEM), 0
+                self.meta.append((name, shape, AF_VEC, nfull, 0, n, 0)); nfull += pad4(n)
+            elif len(shape) == 2:
+                R, C = shape
+                if stride != (C, 1) and not (R == 1 or C == 1):
+                    raise ValueError(f"Adafactor: 2-D parameter {name!r} is not row-major contiguous (strides {stride})")
+                nct, nrb = -(-C // _AF_TC), -(-R // _AF_TR)
+                r.update(kind=AF_MAT, R=R, C=C, s_r=C, row_off=nrow, col_off=ncol, rowp_off=nws, colp_off=nws + R * nct)
+                nws += R * nct + nrb * C
+                items, fitems = nrb * nct, -(-max(R, C) // 256)
+                self.meta.append((name, shape, AF_MAT, nrow, ncol, R, C)); nrow += pad4(R); ncol += pad4(C)
+            elif len(shape) == 4 and shape[2] <= 3 and shape[3] <= 3:
+                O, I, kh, kw = shape
+                dense, expect = True, 1
+                for ext, st in sorted(((e, s) for e, s in zip(shape, stride) if e > 1), key=lambda es: es[1]):
+                    dense, expect = dense and st == expect, expect * ext
+                if not dense:
+                    raise ValueError(f"Adafactor: 4-D parameter {name!r} is not dense (shape {shape}, strides {stride})")
+                r.update(kind=AF_TILE, outer=O, inner=I, R=kh, C=kw, s_outer=stride[0], s_inner=stride[1], s_r=stride[2], s_c=stride[3],
+                         row_off=nrow, col_off=ncol)
+                items, fitems = -(-(O * -(-I // 4)) // 256), 0
+                self.meta.append((name, shape, AF_TILE, nrow, ncol, O * I * kh, O * I * kw)); nrow += pad4(O * I * kh); ncol += pad4(O * I * kw)
+            else:
+                raise ValueError(f"Adafactor: parameter {name!r} of shape {shape} is none of the supported kinds (1-D, 2-D, or 4-D "
+                                 "[O, I, kh, kw] with kh, kw <= 3)")
+            rows.append(r)
+            item0 += items; fitem0 += fitems
+        assert rows, "Adafactor: no tensor"
+        for r in rows:
+            r["rowp_off"] += item0; r["colp_off"] += item0            # the tile partials lie behind the per-item partials
+        arr = np.array([tuple(r[k] for k in AF_DESC_DTYPE.names) for r in rows], dtype=AF_DESC_DTYPE)
+        assert arr.dtype.itemsize == lib().hcp_adafactor_desc_bytes()
+        self.count, self.items, self.fitems = len(rows), item0, fitem0
+        self.host = arr
+        self.descs = torch.from_numpy(arr.view(np.uint8).copy()).to(device)
+        z = lambda n: torch.zeros(max(n, 4), dtype=torch.float32, device=device)
+        self.row, self.col, self.full = z(nrow), z(ncol), z(nfull)
+        self.ws, self.tstat, self.scal = z(item0 + nws), z(4 * len(rows)), z(4)
+
+    def tensors(self):
+        """What a step mutates (the workspace included: a captured step replays into the same buffers)."""
+        return [self.row, self.col, self.full, self.tstat, self.scal]
+
+    def views(self, i):
+        """State of tensor i with the installed class's names and shapes (views: writing them loads a checkpoint)."""
+        name, shape, kind, o1, o2, n1, n2 = self.meta[i]
+        out = {"RMS": self.tstat[4 * i]}
+        if kind == AF_VEC:
+            out["exp_avg_sq"] = self.full[o1:o1 + n1].view(shape)
+        else:
+            out["exp_avg_sq_row"] = self.row[o1:o1 + n1].view(shape[:-1])
+            out["exp_avg_sq_col"] = self.col[o2:o2 + n2].view(shape[:-2] + shape[-1:])
+        return out
+
+
+def adafactor_step(p, g, table, lr, step, *, m=None, eps=(1e-30, 1e-3), clip_threshold=1.0, decay_rate=-0.8, beta1=None, weight_decay=0.0,
+                   scale_parameter=True, relative_step=True, warmup_init=False, sumsq_t=None, grad_scale=1.0, max_norm=0.0):
+    """transformers.optimization.Adafactor.step over every tensor of `table` inside the flat bucket (p, g[, m]); lr: device scalar or
+    None (relative_step); step: device int32 counter, incremented.  g is left zero."""
+    for t in (p, g) + ((m,) if m is not None else ()):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel()
+    assert (m is None) == (beta1 is None), "beta1 needs the first-moment buffer m (and only then)"
+    assert step.dtype == torch.int32 and (lr is None or lr.dtype == torch.float32)
+    if lr is None and not relative_step:
+        raise ValueError("Adafactor: lr is required without relative_step")
+    assert int(table.host["off"].max()) < p.numel() and table.descs.device == p.device
+    _chk(lib().hcp_adafactor_step(_p(p), _p(g), _p(m), _p(table.row), _p(table.col), _p(table.full), _p(table.descs), table.count,
+                                  table.items, table.fitems, _p(table.ws), table.ws.numel() * 4, _p(table.tstat), _p(table.scal),
+                                  _p(lr), float(eps[0]), float(eps[1]), float(clip_threshold), float(decay_rate),
+                                  float(beta1 if beta1 is not None else 0.0), float(weight_decay), int(bool(scale_parameter)),
+                                  int(bool(relative_step)), int(bool(warmup_init)), _p(sumsq_t), float(grad_scale), float(max_norm),
+                                  _p(step), _stream(p)), "hcp_adafactor_step")
 
 
 def cast_f32_bf16(src, dst, scale=1.0, zero_src=False):

@@ -1,5 +1,6 @@
 """Seam 4 (``train.optimizer``, train_base.yaml:37-40 -> train_ac.py:370: ``cfg.train.optimizer(params=params_group)``): a
-``torch.optim.Optimizer`` whose step is the fused AdamW kernel (csrc/optim.hip).
+``torch.optim.Optimizer`` whose step is the fused AdamW kernel (csrc/optim.hip) — and, for the reference's Lion_optimizer.yaml and
+FT_sdxl.yaml examples, ``FusedLion`` / ``FusedAdafactor`` over the same flat runs (csrc/optim_factored.hip).
 
 The reference trainer clips with ``accelerator.clip_grad_norm_`` before ``optimizer.step()`` (train_ac.py:485-491), so the step
 here is plain AdamW (decoupled weight decay, bias correction as torch.optim.AdamW).  Parameters whose storage is adjacent — all
@@ -18,9 +19,14 @@ def _dense_flat(t):
     return t.as_strided((t.numel(),), (1,), t.storage_offset())
 
 
-class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+class _FusedFlat(torch.optim.Optimizer):
+    """What the fused optimizers share: parameters with adjacent storage are stepped as flat runs (one launch sequence per run per param
+    group), the runs are checked against the parameters' pointers, the kernels' raw writes are reported to autograd's version counters,
+    zero_grad clears a run with one fill, and state_dict() / load_state_dict() speak the per-parameter layout of the class each one
+    replaces.  A subclass supplies `_init_run` (its flat state), `_step_run` (its kernel), `_param_state` / `_load_param_state`."""
+
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
         self._runs = {}            # group index -> (sampled signature, [run], full signature)
         self._nsteps = {}          # group index -> steps since the runs were built (full pointer check every FULL_CHECK_EVERY)
 
@@ -30,24 +36,26 @@ class FusedAdamW(torch.optim.Optimizer):
             if p.grad is None:
                 continue
             if p.dtype != torch.float32 or p.grad.dtype != torch.float32:
-                raise TypeError("FusedAdamW keeps fp32 master parameters (the reference: fp32 params under autocast)")
+                raise TypeError(f"{type(self).__name__} keeps fp32 master parameters (the reference: fp32 params under autocast)")
             items.append((p.untyped_storage().data_ptr(), p.storage_offset(), p.numel(), p,
                           p.grad.untyped_storage().data_ptr(), p.grad.storage_offset()))
         items.sort(key=lambda it: (it[0], it[1]))
         runs, cur = [], None
         for sp, so, n, p, gp, go in items:
             if cur and cur["sp"] == sp and cur["gp"] == gp and cur["so"] + cur["n"] == so and cur["go"] + cur["n"] == go:
-                cur["n"] += n
+                cur["members"].append((p, cur["n"])); cur["n"] += n
             else:
-                cur = dict(sp=sp, gp=gp, so=so, go=go, n=n, p=p)
+                cur = dict(sp=sp, gp=gp, so=so, go=go, n=n, p=p, members=[(p, 0)])
                 runs.append(cur)
         out = []
         for r in runs:
             p, n = r["p"], r["n"]
             pf = _dense_flat(p).as_strided((n,), (1,), r["so"])
             gf = _dense_flat(p.grad).as_strided((n,), (1,), r["go"])
-            out.append(dict(p=pf, g=gf, m=torch.zeros_like(pf), v=torch.zeros_like(pf),
-                            lr=torch.zeros(1, dtype=torch.float32, device=pf.device), step=torch.zeros(1, dtype=torch.int32, device=pf.device)))
+            run = dict(p=pf, g=gf, members=r["members"],         # members: [(parameter, its offset in the run)]
+                       lr=torch.zeros(1, dtype=torch.float32, device=pf.device), step=torch.zeros(1, dtype=torch.int32, device=pf.device))
+            self._init_run(run, group)
+            out.append(run)
         return out
 
     FULL_CHECK_EVERY = 64
@@ -76,16 +84,15 @@ class FusedAdamW(torch.optim.Optimizer):
                     moved = self._sig(group, full=True) != cached[2]
             if cached is None or moved:
                 if cached is not None:
-                    raise RuntimeError("FusedAdamW: the set of parameters with gradients (or their storage) changed between steps; "
-                                       "the flat AdamW moments cannot follow")
+                    raise RuntimeError(f"{type(self).__name__}: the set of parameters with gradients (or their storage) changed between "
+                                       "steps; the flat optimizer state cannot follow")
                 cached = (sig, self._build_runs(group), self._sig(group, full=True))
                 self._runs[gi] = cached
                 self._apply_resume(group, cached[1])
-            b1, b2 = group["betas"]
             for r in cached[1]:
-                r["lr"].fill_(group["lr"])
-                K.adamw_clip_fused(r["p"], r["g"], r["m"], r["v"], r["lr"], r["step"], beta1=b1, beta2=b2, eps=group["eps"],
-                                   weight_decay=group["weight_decay"], sumsq_t=None, grad_scale=1.0, max_norm=0.0)
+                if group["lr"] is not None:
+                    r["lr"].fill_(group["lr"])
+                self._step_run(r, group)
         self._bump_versions()
         return loss
 
@@ -129,34 +136,35 @@ class FusedAdamW(torch.optim.Optimizer):
         for p in ps:                                       # any torch: an in-place op on an empty slice bumps the counter
             p[:0].add_(0)
 
-    # ---- checkpoint / resume: the flat moments live outside `self.state` (one tensor per contiguous run, not per parameter)
+    # ---- checkpoint / resume: the flat state lives outside `self.state` (per contiguous run, not per parameter)
+    @staticmethod
+    def _cut(flat, p, off):
+        """The slice of a flat run buffer that belongs to parameter p, with p's own shape and strides."""
+        return flat[off:off + p.numel()].as_strided(p.shape, p.stride())
+
     def state_dict(self):
-        """torch's layout ({'state': {index: {...}}, 'param_groups': [...]}) with PER-PARAMETER exp_avg / exp_avg_sq / step cut out of the
-        flat runs, so that the file resumes a torch.optim.AdamW as well as a FusedAdamW (train_ac.py:370 builds either from the same cfg)."""
+        """torch's layout ({'state': {index: {...}}, 'param_groups': [...]}) with the PER-PARAMETER state of the replaced class cut out of
+        the flat runs, so that the file resumes that class as well as this one (train_ac.py:370 builds either from the same cfg)."""
         base = super().state_dict()
         state, index = {}, 0
         ids = {}
         for group in self.param_groups:
             for p in group["params"]:
                 ids[id(p)] = index; index += 1
-        for gi, group in enumerate(self.param_groups):
+        for gi in range(len(self.param_groups)):
             cached = self._runs.get(gi)
             if cached is None:
                 continue
             for r in cached[1]:
-                base_ptr, step = r["p"].data_ptr(), r["step"].item()
-                for p in group["params"]:
-                    off = (p.data_ptr() - base_ptr) // 4
-                    if p.grad is None or off < 0 or off + p.numel() > r["p"].numel() or p.untyped_storage().data_ptr() != r["p"].untyped_storage().data_ptr():
-                        continue
-                    view = lambda flat: flat[off:off + p.numel()].as_strided(p.shape, p.stride()).clone()
-                    state[ids[id(p)]] = {"step": torch.tensor(float(step)), "exp_avg": view(r["m"]), "exp_avg_sq": view(r["v"])}
+                step = r["step"].item()
+                for k, (p, off) in enumerate(r["members"]):
+                    state[ids[id(p)]] = self._param_state(r, k, p, off, step)
         base["state"] = state
         return base
 
     def load_state_dict(self, state_dict):
-        """Moments and step counts of a file written by state_dict() above or by torch.optim.AdamW over the same parameters; the flat
-        runs are (re)built on the first step, so the values wait in `_resume` until then."""
+        """State of a file written by state_dict() above or by the replaced class over the same parameters; the flat runs are (re)built
+        on the first step, so the values wait in `_resume` until then."""
         super().load_state_dict({"state": {}, "param_groups": state_dict["param_groups"]})
         order = [p for group in self.param_groups for p in group["params"]]
         self._resume = {id(order[int(i)]): st for i, st in state_dict.get("state", {}).items()}
@@ -167,13 +175,102 @@ class FusedAdamW(torch.optim.Optimizer):
         if not res:
             return
         for r in runs:
-            base_ptr = r["p"].data_ptr()
-            for p in group["params"]:
+            for k, (p, off) in enumerate(r["members"]):
                 st = res.get(id(p))
-                off = (p.data_ptr() - base_ptr) // 4
-                if st is None or p.grad is None or off < 0 or off + p.numel() > r["p"].numel() or \
-                        p.untyped_storage().data_ptr() != r["p"].untyped_storage().data_ptr():
+                if st is None:
                     continue
-                for name, flat in (("exp_avg", r["m"]), ("exp_avg_sq", r["v"])):
-                    flat[off:off + p.numel()].as_strided(p.shape, p.stride()).copy_(st[name].to(flat.device))
+                self._load_param_state(r, k, p, off, st)
                 r["step"].fill_(int(float(st["step"])))
+
+
+class FusedAdamW(_FusedFlat):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def _init_run(self, r, group):
+        r["m"], r["v"] = torch.zeros_like(r["p"]), torch.zeros_like(r["p"])
+
+    def _step_run(self, r, group):
+        b1, b2 = group["betas"]
+        K.adamw_clip_fused(r["p"], r["g"], r["m"], r["v"], r["lr"], r["step"], beta1=b1, beta2=b2, eps=group["eps"],
+                           weight_decay=group["weight_decay"], sumsq_t=None, grad_scale=1.0, max_norm=0.0)
+
+    def _param_state(self, r, k, p, off, step):
+        return {"step": torch.tensor(float(step)), "exp_avg": self._cut(r["m"], p, off).clone(), "exp_avg_sq": self._cut(r["v"], p, off).clone()}
+
+    def _load_param_state(self, r, k, p, off, st):
+        for name, flat in (("exp_avg", r["m"]), ("exp_avg_sq", r["v"])):
+            self._cut(flat, p, off).copy_(st[name].to(flat.device))
+
+
+class FusedLion(_FusedFlat):
+    """lion_pytorch.Lion (cfgs/train/examples/Lion_optimizer.yaml) with its constructor and its per-parameter state (`exp_avg`)."""
+
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.99), weight_decay=0.0):
+        if lr <= 0 or not all(0.0 <= b <= 1.0 for b in betas):
+            raise ValueError("FusedLion: lr > 0 and betas in [0, 1]")
+        super().__init__(params, dict(lr=lr, betas=betas, weight_decay=weight_decay))
+
+    def _init_run(self, r, group):
+        r["m"] = torch.zeros_like(r["p"])
+
+    def _step_run(self, r, group):
+        b1, b2 = group["betas"]
+        K.lion_clip_fused(r["p"], r["g"], r["m"], r["lr"], r["step"], beta1=b1, beta2=b2, weight_decay=group["weight_decay"])
+
+    def _param_state(self, r, k, p, off, step):
+        return {"exp_avg": self._cut(r["m"], p, off).clone()}
+
+    def _load_param_state(self, r, k, p, off, st):
+        self._cut(r["m"], p, off).copy_(st["exp_avg"].to(r["m"].device))
+
+    def _apply_resume(self, group, runs):          # (lion_pytorch keeps no step count)
+        res = getattr(self, "_resume", None)
+        if res:
+            for r in runs:
+                for k, (p, off) in enumerate(r["members"]):
+                    if id(p) in res:
+                        self._load_param_state(r, k, p, off, res[id(p)])
+
+
+class FusedAdafactor(_FusedFlat):
+    """transformers.optimization.Adafactor (cfgs/train/examples/FT_sdxl.yaml) with its constructor, its checks and its per-parameter state
+    (`step`, `RMS`, `exp_avg_sq_row` + `exp_avg_sq_col` or `exp_avg_sq`, `exp_avg` with beta1).  Every run of adjacent parameters is
+    stepped from one descriptor table (kernels.AdafactorTable): seven launches per run whatever the number of tensors."""
+
+    def __init__(self, params, lr=None, eps=(1e-30, 1e-3), clip_threshold=1.0, decay_rate=-0.8, beta1=None, weight_decay=0.0,
+                 scale_parameter=True, relative_step=True, warmup_init=False):
+        if lr is not None and relative_step:
+            raise ValueError("Cannot combine manual `lr` and `relative_step=True` options")
+        if warmup_init and not relative_step:
+            raise ValueError("`warmup_init=True` requires `relative_step=True`")
+        super().__init__(params, dict(lr=lr, eps=eps, clip_threshold=clip_threshold, decay_rate=decay_rate, beta1=beta1,
+                                      weight_decay=weight_decay, scale_parameter=scale_parameter, relative_step=relative_step,
+                                      warmup_init=warmup_init))
+
+    def _init_run(self, r, group):
+        names = {id(p): f"param_groups[{gi}]['params'][{i}]" for gi, g in enumerate(self.param_groups) for i, p in enumerate(g["params"])}
+        for p, _ in r["members"]:
+            if p.grad.stride() != p.stride():
+                raise ValueError(f"FusedAdafactor: {names.get(id(p), '?')} and its gradient are laid out differently")
+        r["table"] = K.AdafactorTable([(names.get(id(p), "?"), off, p.shape, p.stride()) for p, off in r["members"]], r["p"].device)
+        r["m"] = torch.zeros_like(r["p"]) if group["beta1"] is not None else None
+
+    def _step_run(self, r, group):
+        K.adafactor_step(r["p"], r["g"], r["table"], r["lr"] if group["lr"] is not None else None, r["step"], m=r["m"], eps=group["eps"],
+                         clip_threshold=group["clip_threshold"], decay_rate=group["decay_rate"], beta1=group["beta1"],
+                         weight_decay=group["weight_decay"], scale_parameter=group["scale_parameter"],
+                         relative_step=group["relative_step"], warmup_init=group["warmup_init"])
+
+    def _param_state(self, r, k, p, off, step):
+        st = {"step": int(step)}
+        st.update({name: v.clone() for name, v in r["table"].views(k).items()})
+        if r["m"] is not None:
+            st["exp_avg"] = self._cut(r["m"], p, off).clone()
+        return st
+
+    def _load_param_state(self, r, k, p, off, st):
+        for name, v in r["table"].views(k).items():
+            v.copy_(torch.as_tensor(st[name], dtype=torch.float32).to(v.device))
+        if r["m"] is not None:
+            self._cut(r["m"], p, off).copy_(st["exp_avg"].to(r["m"].device))

@@ -15,6 +15,7 @@ captured once into a hipGraph (two graphs around the all-reduce when world_size 
 per-step ``loss.item()`` sync (train_ac.py:504) is deferred to whenever the caller reads the loss tensor.
 """
 import contextlib
+import math
 
 import torch
 
@@ -43,8 +44,10 @@ class _OptState:
     slices only (optimizer memory and HBM traffic / world).  grad_wire / param_wire 'bf16': the gradients leave, and the updated
     parameters return, as bf16 (half the bytes on xGMI; the fp32 masters of a slice then live on its owner only)."""
 
-    def __init__(self, bucket, lr, device, segments=None, comm=None, shard=False, grad_wire="fp32", param_wire="fp32"):
+    def __init__(self, bucket, lr, device, segments=None, comm=None, shard=False, grad_wire="fp32", param_wire="fp32", opt=None):
         self.bucket = bucket
+        self.opt = opt or {"type": "adamw"}              # the optimizer's own state follows its type (NativeTrainer `optimizer=`)
+        kind = self.opt["type"]
         n = bucket.params.numel()
         self.shard = bool(shard and comm is not None and (comm.world > 1 or shard == "force"))
         self.parts = []
@@ -64,17 +67,65 @@ class _OptState:
             self.own = n
         self.segments = [(o, m) for o, m, _ in segments] if segments else [(0, self.own)]
         self.base_lrs = [l for _, _, l in segments] if segments else [lr]
-        self.exp_avg = torch.zeros(self.own, dtype=torch.float32, device=device)
-        self.exp_avg_sq = torch.zeros(self.own, dtype=torch.float32, device=device)
+        # adamw: both moments; lion: the momentum; adafactor: the first moment only with beta1, factored second moments in the tables
+        first = kind != "adafactor" or self.opt.get("beta1") is not None
+        self.exp_avg = torch.zeros(self.own, dtype=torch.float32, device=device) if first else None
+        self.exp_avg_sq = torch.zeros(self.own, dtype=torch.float32, device=device) if kind == "adamw" else None
+        self.tables = []
+        if kind == "adafactor":                          # one descriptor table per lr segment (offsets relative to the segment)
+            assert not self.shard, "Adafactor factors whole tensors: not sharded"
+            base = bucket.params.data_ptr()
+            rows = sorted(((p.data_ptr() - base) // 4, name, p) for name, p in _bucket_tensors(bucket))
+            for o, m in self.segments:
+                seg = [(name, off - o, p.shape, p.stride()) for off, name, p in rows if o <= off < o + m]
+                assert seg and all(off + math.prod(sh) <= m for _, off, sh, _ in seg), "a tensor straddles two lr segments"
+                self.tables.append(K.AdafactorTable(seg, device))
+            assert sum(t.count for t in self.tables) == len(rows), "every tensor of the bucket belongs to one lr segment"
         self.lrs = [torch.full((1,), l, dtype=torch.float32, device=device) for l in self.base_lrs]
         # (the kernel advances its step counter per launch: one counter per segment / per chunk of a sharded bucket, in lockstep)
         self.steps = [torch.zeros(1, dtype=torch.int32, device=device) for _ in range(max(len(self.base_lrs), len(self.parts)))]
         self.lr, self.step_count = self.lrs[0], self.steps[0]
         self.sumsq = torch.zeros(1, dtype=torch.float32, device=device)
+        # lion / adafactor: the norm is summed without atomics (K.sumsq_ordered), so the whole step is bit-reproducible; adamw keeps K.sumsq
+        self.sumsq_part = torch.zeros(K.SUMSQ_PARTIALS, dtype=torch.float32, device=device) if kind != "adamw" else None
 
     def tensors(self):
         """Everything a step mutates besides the bucket itself (snapshot / restore around the graph warm-up)."""
-        return [self.exp_avg, self.exp_avg_sq, self.sumsq] + self.lrs + self.steps + ([self.ema] if hasattr(self, "ema") else [])
+        own = [t for t in (self.exp_avg, self.exp_avg_sq) if t is not None] + [x for t in self.tables for x in t.tensors()]
+        return own + [self.sumsq] + self.lrs + self.steps + ([self.ema] if hasattr(self, "ema") else [])
+
+
+def _bucket_tensors(bucket):
+    """[(name, parameter)] of a flat bucket: HostBucket.named, the LoRA factors of a LoraBucket, the words of a PTBucket."""
+    if getattr(bucket, "named", None) is not None:
+        return list(bucket.named)
+    if hasattr(bucket, "blocks"):
+        return [(f"lora_block[{i}].{n}", getattr(blk.layer, n)) for i, blk in enumerate(bucket.blocks) for n in ("W_down", "W_up")]
+    return list(zip(bucket.names, bucket.words))
+
+
+LION_DEFAULTS = dict(betas=(0.9, 0.99))                                         # lion_pytorch.Lion
+ADAFACTOR_DEFAULTS = dict(eps=(1e-30, 1e-3), clip_threshold=1.0, decay_rate=-0.8, beta1=None, scale_parameter=True,
+                          relative_step=True, warmup_init=False)                # transformers.optimization.Adafactor
+
+
+def _optimizer_cfg(optimizer):
+    """NativeTrainer's `optimizer=` argument -> {'type': ..., the class's keyword arguments with its defaults filled in}."""
+    cfg = dict(optimizer or {"type": "adamw"})
+    kind = cfg.get("type")
+    known = {"adamw": {}, "lion": LION_DEFAULTS, "adafactor": ADAFACTOR_DEFAULTS}
+    if kind not in known:
+        raise ValueError(f"Unknown optimizer type {kind!r}: 'adamw', 'lion' or 'adafactor'")
+    extra = set(cfg) - {"type", "weight_decay", "lr"} - set(known[kind])
+    if extra:
+        raise ValueError(f"optimizer type {kind!r} takes no {sorted(extra)}")
+    cfg = {**known[kind], **cfg}
+    if kind == "adafactor":
+        if cfg.get("lr") is not None and cfg["relative_step"]:
+            raise ValueError("Cannot combine manual `lr` and `relative_step=True` options")
+        if cfg["warmup_init"] and not cfg["relative_step"]:
+            raise ValueError("`warmup_init=True` requires `relative_step=True`")
+    return cfg
 
 
 FP32_WIRE = 10      # chunk ids >= 10: parameters the kernels read as fp32 (biases, norm affine) — never rounded on the wire
@@ -129,7 +180,8 @@ class NativeTrainer:
                  scale_lr_factor=1.0, process_group=None, use_graph=False, loss_weight=1.0, num_train_timesteps=1000,
                  overlap_wgrad=False, grouped_wgrad=True, train_cfg=None, plugins=None, ema=None, loss_cfg=None, text_encoder=None,
                  lora_te_cfg=None, comm=None, shard_optimizer=None, gradient_accumulation_steps=1, loss_type="eps",
-                 overlap_exchange=False, grad_wire="fp32", param_wire="fp32", pt_cfg=None, pt_words=None, pt_weight_decay=5e-4):
+                 overlap_exchange=False, grad_wire="fp32", param_wire="fp32", pt_cfg=None, pt_words=None, pt_weight_decay=5e-4,
+                 optimizer=None):
         """lora_cfg: the reference's ``lora_unet`` list ({layers, rank, alpha, lr, ...}); train_cfg: its ``unet`` list
         ({layers, lr}) of host modules to fine-tune in full (DreamBooth.yaml:6-10 uses ``layers: ['']`` = everything);
         plugins: [(plugin module, lr)] — trainable hook plugins such as controlnet.ControlNetHipPlugin (make_plugin,
@@ -159,12 +211,25 @@ class NativeTrainer:
         with one lr segment per word (``scale_lr_pt``: the same scale_lr_factor), stepped by the fused AdamW with pt_weight_decay
         (train_base.yaml:42-55 ``optimizer_pt``).  They join the global-norm clip only when the text encoder trains too
         (TE_unet.trainable_parameters() then holds the hook's emb_train, train_ac.py:483-490); the exchange and the captured step
-        cover them like every bucket."""
+        cover them like every bucket.
+        optimizer: None or {'type': 'adamw'} = the fused AdamW with this constructor's betas / eps / weight_decay; {'type': 'lion', 'betas':
+        (0.9, 0.99)} = lion_pytorch.Lion (Lion_optimizer.yaml); {'type': 'adafactor', ...} with the keyword names and defaults of
+        transformers.optimization.Adafactor (FT_sdxl.yaml: relative_step False, weight_decay 1e-3) — without relative_step the step size
+        is each item's lr, with it the lrs are ignored as that class ignores them.  'weight_decay' in the dict overrides this
+        constructor's.  The choice applies to EVERY bucket (LoRA, text-encoder LoRA, host buckets, plugins, words — those with
+        pt_weight_decay).  Lion is elementwise and shards like AdamW; Adafactor needs whole tensors (row / column statistics), so its host
+        buckets stay on the unsharded all-reduce path at world > 1 and an explicit shard_optimizer raises."""
+        self.opt_cfg = _optimizer_cfg(optimizer)
         self.unet = unet
         self.device = next(unet.parameters()).device
         self.comm = comm if comm is not None else make_comm(self.device, process_group)
         self.world = self.comm.world
         shard = (self.world > 1) if shard_optimizer is None else bool(shard_optimizer and self.world > 1)
+        if self.opt_cfg["type"] == "adafactor":
+            if shard_optimizer:
+                raise ValueError("shard_optimizer with Adafactor: its second moments are row / column statistics of WHOLE tensors, which "
+                                 "a slice of the flat bucket does not hold; leave shard_optimizer unset (one all-reduce per bucket)")
+            shard = False
         if shard_optimizer == "force":        # tests: the sharded code path (chunks, side stream, wire casts) on ONE rank
             shard = "force"
         if grad_wire not in ("fp32", "bf16") or param_wire not in ("fp32", "bf16"):
@@ -190,18 +255,18 @@ class NativeTrainer:
                     if id(p_) not in seen and "lora_block_" not in full:
                         seen.add(id(p_)); params.append((full, p_))
             hb = HostBucket(unet, params, pad_multiple=pad, chunk_of=_chunker(self._overlap, param_wire, bf16_ids=_bf16_consumed(unet)) if shard else None)
-            self.host_buckets.append(_OptState(hb, item.get("lr", lr) * scale_lr_factor, self.device, comm=self.comm, shard=shard, **wires))
+            self.host_buckets.append(_OptState(hb, item.get("lr", lr) * scale_lr_factor, self.device, comm=self.comm, shard=shard, opt=self.opt_cfg, **wires))
         self.plugins = []
         for plugin, plr in (plugins or []):
             plugin.train()
             hb = HostBucket(plugin, list(plugin.named_parameters()), pad_multiple=pad,
                             chunk_of=_chunker(False, param_wire, unet_names=False, bf16_ids=_bf16_consumed(plugin)) if shard else None)
-            self.host_buckets.append(_OptState(hb, plr * scale_lr_factor, self.device, comm=self.comm, shard=shard, **wires))
+            self.host_buckets.append(_OptState(hb, plr * scale_lr_factor, self.device, comm=self.comm, shard=shard, opt=self.opt_cfg, **wires))
             self.plugins.append(plugin)
         self.param_groups, self.lora_group, self.bucket = make_lora(unet, lora_cfg) if lora_cfg else ([], None, None)
         assert self.bucket is not None or self.host_buckets or lora_te_cfg or pt_cfg, "nothing to train: no LoRA layer matched and no host group given"
         self._lora_state = (_OptState(self.bucket, lr * scale_lr_factor, self.device,
-                                      segments=self._segments(self.param_groups, self.bucket, scale_lr_factor, lr))
+                                      segments=self._segments(self.param_groups, self.bucket, scale_lr_factor, lr), opt=self.opt_cfg)
                             if self.bucket is not None else None)
         if self._lora_state is not None:      # historical attribute names (tests / tools read them)
             st = self._lora_state
@@ -214,7 +279,7 @@ class NativeTrainer:
                 te_groups, self.lora_te_group, self.te_bucket = make_lora(text_encoder, lora_te_cfg)
                 assert self.te_bucket is not None, "lora_text_encoder matched no layer"
                 self._te_state = _OptState(self.te_bucket, lr * scale_lr_factor, self.device,
-                                           segments=self._segments(te_groups, self.te_bucket, scale_lr_factor, lr))
+                                           segments=self._segments(te_groups, self.te_bucket, scale_lr_factor, lr), opt=self.opt_cfg)
         elif lora_te_cfg:
             raise ValueError("lora_te_cfg needs the text_encoder module")
         self.pt_bucket, self._pt_state, self.pt_words = None, None, {}
@@ -231,7 +296,7 @@ class NativeTrainer:
             self.pt_bucket = PTBucket(hook, words)
             self.pt_words = dict(zip(self.pt_bucket.names, self.pt_bucket.words))
             self.pt_hook = hook
-            self._pt_state = _OptState(self.pt_bucket, lr, self.device, segments=self.pt_bucket.segments)
+            self._pt_state = _OptState(self.pt_bucket, lr, self.device, segments=self.pt_bucket.segments, opt=self.opt_cfg)
             self._pt_state.weight_decay = pt_weight_decay
             self._pt_state.clipped = self.te_bucket is not None
             self._pt_state.no_ema = True
@@ -381,6 +446,28 @@ class NativeTrainer:
                 if not st.shard:
                     self.comm.all_reduce_(st.bucket.grads)
 
+    @staticmethod
+    def _sumsq(st, g):
+        if st.sumsq_part is None:
+            K.sumsq(g, st.sumsq)
+        else:
+            K.sumsq_ordered(g, st.sumsq, st.sumsq_part)
+
+    def _fused_step(self, st, p, g, off, n, lr_t, step_t, table, total, max_norm):
+        """One fused clip + optimizer launch sequence over p / g; off, n: where their state lies in st's flat buffers."""
+        o = st.opt
+        clip = dict(sumsq_t=total, grad_scale=1.0 / self.world, max_norm=max_norm)
+        wd = getattr(st, "weight_decay", o.get("weight_decay", self.weight_decay))      # (the words carry pt_weight_decay)
+        if o["type"] == "adamw":
+            K.adamw_clip_fused(p, g, st.exp_avg[off:off + n], st.exp_avg_sq[off:off + n], lr_t, step_t, beta1=self.betas[0],
+                               beta2=self.betas[1], eps=self.eps, weight_decay=wd, **clip)
+        elif o["type"] == "lion":
+            K.lion_clip_fused(p, g, st.exp_avg[off:off + n], lr_t, step_t, beta1=o["betas"][0], beta2=o["betas"][1], weight_decay=wd, **clip)
+        else:
+            K.adafactor_step(p, g, table, lr_t, step_t, m=st.exp_avg[off:off + n] if st.exp_avg is not None else None, eps=o["eps"],
+                             clip_threshold=o["clip_threshold"], decay_rate=o["decay_rate"], beta1=o["beta1"], weight_decay=wd,
+                             scale_parameter=o["scale_parameter"], relative_step=o["relative_step"], warmup_init=o["warmup_init"], **clip)
+
     def optimizer_step(self, early_sent=()):
         """early_sent: ids of the chunks the last backward already reduce-scattered (overlap_exchange)."""
         states = self._states()
@@ -392,9 +479,9 @@ class NativeTrainer:
                         self._exchange_part(st, k)
                 if st.gshard_w is not None:
                     K.cast_bf16_f32(st.gshard_w, st.gshard)
-                K.sumsq(st.gshard, st.sumsq)
+                self._sumsq(st, st.gshard)
             else:
-                K.sumsq(st.bucket.grads, st.sumsq)
+                self._sumsq(st, st.bucket.grads)
         # clip_grad_norm_ over ALL trainable parameters (train_ac.py:485-489): slices add up across ranks (one 4-byte all-reduce)
         total = None
         if sharded:
@@ -412,9 +499,7 @@ class NativeTrainer:
                 for k, (_, lo, hi, own, off) in enumerate(st.parts):
                     mlo, mhi = lo + r * own, lo + (r + 1) * own
                     mine = b.params[mlo:mhi]
-                    K.adamw_clip_fused(mine, st.gshard[off:off + own], st.exp_avg[off:off + own], st.exp_avg_sq[off:off + own], st.lrs[0],
-                                       st.steps[k], beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.weight_decay,
-                                       sumsq_t=total, grad_scale=1.0 / self.world, max_norm=self.max_grad_norm)
+                    self._fused_step(st, mine, st.gshard[off:off + own], off, own, st.lrs[0], st.steps[k], None, total, self.max_grad_norm)
                     if st.pwire is None or st.parts[k][0] >= FP32_WIRE:
                         self.comm.all_gather(mine, b.params[lo:hi])      # every rank holds the updated masters again
                         continue
@@ -429,12 +514,9 @@ class NativeTrainer:
                     b.grads.zero_()                           # zero_grad of the full bucket (the kernel cleared the slice copy only)
                 continue
             clipped = getattr(st, "clipped", True)            # prompt-tuning words outside the clip: textual inversion alone
-            for (off, n), lr_t, step_t in zip(st.segments, st.lrs, st.steps):
-                K.adamw_clip_fused(b.params[off:off + n], b.grads[off:off + n], st.exp_avg[off:off + n], st.exp_avg_sq[off:off + n],
-                                   lr_t, step_t, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
-                                   weight_decay=getattr(st, "weight_decay", self.weight_decay),
-                                   sumsq_t=total if clipped else None, grad_scale=1.0 / self.world,
-                                   max_norm=self.max_grad_norm if clipped else 0.0)
+            for k, ((off, n), lr_t, step_t) in enumerate(zip(st.segments, st.lrs, st.steps)):
+                self._fused_step(st, b.params[off:off + n], b.grads[off:off + n], off, n, lr_t, step_t, st.tables[k] if st.tables else None,
+                                 total if clipped else None, self.max_grad_norm if clipped else 0.0)
         if self.ema_cfg is not None:           # update_ema (train_ac.py:503,517-521)
             for st in states:
                 if hasattr(st, "ema"):

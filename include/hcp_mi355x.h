@@ -272,6 +272,30 @@ int hcp_sumsq_f32(const float* g, long n, float* out, hcpStream_t stream);
 int hcp_adamw_clip_fused(float* p, float* g, float* m, float* v, long n, const float* lr, float beta1, float beta2,
                          float eps, float weight_decay, const float* sumsq, float grad_scale, float max_norm, int* step,
                          hcpStream_t stream);
+/* hcp_sumsq_f32 without atomics: one partial per workgroup (partials: HCP_SUMSQ_PARTIALS floats), added in workgroup order by a second
+ * launch.  The same bits on every run: with it a clip + Lion / Adafactor step is reproducible end to end. */
+#define HCP_SUMSQ_PARTIALS 2048
+int hcp_sumsq_ordered_f32(const float* g, long n, float* out, float* partials, hcpStream_t stream);
+/* lion_pytorch.Lion (cfgs/train/examples/Lion_optimizer.yaml) on one flat fp32 bucket, conventions of hcp_adamw_clip_fused (grad_scale,
+ * global-norm clip from *sumsq, device-resident lr, *step incremented, g left zero):
+ * p *= 1 - lr wd;  p -= lr sign(beta1 m + (1 - beta1) g), sign(0) = 0;  m = beta2 m + (1 - beta2) g.  The betas are doubles: 1 - beta
+ * is formed in double and rounded once. */
+int hcp_lion_clip_fused(float* p, float* g, float* m, long n, const float* lr, double beta1, double beta2, float weight_decay,
+                        const float* sumsq, float grad_scale, float max_norm, int* step, hcpStream_t stream);
+/* transformers.optimization.Adafactor.step (cfgs/train/examples/FT_sdxl.yaml) for every tensor of one flat fp32 bucket, after the same
+ * grad_scale / global-norm clip prologue; g is left zero, *step incremented.  descs = device array of `count` 112-byte rows
+ * {long off, row_off, col_off, full_off, rowp_off, colp_off, s_outer, s_inner, s_r, s_c; int kind, outer, inner, R, C, item0, fitem0, pad;}
+ * sorted by item0 (csrc/optim_factored.hip AfDesc; built by kernels.adafactor_table).  kind 0 VEC (1-D, unfactored: state in `full`),
+ * 1 MAT (row-major [R, C]: `row` [R], `col` [C]), 2 TILE ([O, I, kh, kw], kh, kw <= 3, any dense strides: `row` [O, I, kh], `col`
+ * [O, I, kw]).  m: first moments laid out as the bucket (NULL: beta1 None, the beta1 argument is then ignored).  workspace: the floats
+ * the table asks for (one per work item, then the MAT tile partials); tstat: 4 floats per tensor, [0] = RMS(p) of the step; scal: 4
+ * floats.  lr: device scalar (NULL with relative_step).  Seven launches whatever `count` is; no atomics: bit-reproducible. */
+int hcp_adafactor_desc_bytes(void);
+int hcp_adafactor_step(float* p, float* g, float* m, float* row, float* col, float* full, const void* descs, int count,
+                       int total_items, int total_fitems, float* workspace, size_t workspace_bytes, float* tstat, float* scal,
+                       const float* lr, float eps1, float eps2, float clip_threshold, float decay_rate, double beta1,
+                       float weight_decay, int scale_parameter, int relative_step, int warmup_init, const float* sumsq,
+                       float grad_scale, float max_norm, int* step, hcpStream_t stream);
 /* ModelEMA.update (reference hcpdiff/utils/ema.py:17-27) over a flat bucket: ema <- lerp(ema, p, 1 - decay(step)) */
 int hcp_ema_update(float* ema, const float* p, long n, const int* step, float inv_gamma, float power, float decay_max,
                    hcpStream_t stream);
