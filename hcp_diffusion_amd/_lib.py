@@ -97,6 +97,9 @@ _PROTOTYPES = {
     "hcp_softmax_rows": (I, [P, L, P, L, I, I, F, P]),
     "hcp_vae_latent_sample": (I, [P, P, P, P, P, I, I, L, F, P]),
     "hcp_mse_masked_mean": (I, [P, P, P, I, P, P, P, I, I, I, F, P]),
+    # pred2, target, mask, mask_channels, sample_weight, timesteps, cfg_lo, cfg_hi, rate_kind, num_train_timesteps, loss, grad2,
+    # partials (2048 floats), B, C, HW, weight, stream
+    "hcp_cfg_mse_masked_mean": (I, [P, P, P, I, P, P, F, F, I, I, P, P, P, I, I, I, F, P]),
     # L, ldl, l_lo, R, ldr, out, ldo, M, P, Q, scale, transpose_out, workspace, workspace_bytes, stream
     "hcp_lora_wgrad": (I, [P, I, I, P, I, P, I, I, I, I, F, I, P, c_size_t, P]),
     # U, ldu, x, ldx, K, grad_down, T, ldt, dY, ldy, N, grad_up, M, r, scale, workspace, workspace_bytes, stream

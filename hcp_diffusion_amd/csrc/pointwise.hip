@@ -6,6 +6,7 @@
 //  * nearest-2x upsample backward         (Upsample2D, unet_struct.txt:390-393)
 //  * sinusoidal timestep embedding        (Timesteps(flip_sin_to_cos=True, freq_shift=0), unet_struct.txt:3)
 //  * DDPM add_noise and masked-MSE loss   (reference train_ac.py:437-447, 506-515)
+//  * DreamArtist CFG combine + masked MSE   (reference models/cfg_context.py:12-39)
 // All kernels are grid-stride over 16-byte (8 x bf16) vectors.
 #include "hcp_common.h"
 
@@ -206,6 +207,82 @@ HCP_KERNEL(256) mse_kernel(const float* pred, const float* target, const float* 
     }
     acc = hcp_wave_sum(acc);
     if ((threadIdx.x & 63) == 0) hcp_atomic_add(loss, acc * scale);
+}
+
+// DreamArtist loss (reference models/cfg_context.py:23-39 + train_ac.py:506-515): the classifier-free-guidance combination of the two
+// halves of pred2 = [negative rows ; positive rows], its masked MSE against target, and the gradient of both halves, in one pass:
+//   e = u + s_b (c - u);  partial sums of (e - target)^2 m;  grad2[neg] = (1 - s_b) g, grad2[pos] = s_b g,  g = 2 scale (e - target) m
+//   s_b = (hi - lo) rate_b + lo;  r = t_b / (T - 1);  rate_b = r (kind 0 'ln') | cos((r - 1) pi/2) (1 'cos') | 1 - cos(r pi/2) (2 'cos2')
+// A work item is one 256-thread slice of ONE sample (chunks per sample), so s_b and sample_weight[b] are formed once per item, never per
+// element.  vec: HW % 4 == 0 and 16-byte aligned buffers -> 16-byte loads / stores (a vector never crosses a channel row of the mask).
+// The loss side runs in double (s_b, e - target, the squares and their sums: a handful of fp64 operations per 20 bytes of traffic), so
+// the loss carries two roundings to fp32 in all — the workgroup's partial and the result — whatever the element count; the gradient is
+// fp32 arithmetic on the rounded difference.  No atomics: every workgroup writes one partial, cfg_mse_finish_kernel adds them in index
+// order.
+HCP_DEVICE double cfg_block_sum(double v, double* red) {       // red [256]: a fixed tree, the same order on every run
+    red[threadIdx.x] = v;
+    HCP_SYNC();
+    for (int k = 128; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+        HCP_SYNC();
+    }
+    return red[0];
+}
+HCP_KERNEL(256) cfg_mse_kernel(const float* pred2, const float* target, const float* mask, int mask_c, const float* sw, const long long* t,
+                               float cfg_lo, float cfg_hi, int rate_kind, int tmax, float* grad2, float* part, int B, int C, int HW,
+                               int chunks, int vec, float scale) {
+    HCP_DYN_SMEM(smem);
+    const long per = (long)C * HW, half = (long)B * per;
+    const long items = (long)B * chunks;
+    const float gs = 2.0f * scale;
+    double acc = 0.0;
+    for (long item = blockIdx.x; item < items; item += gridDim.x) {
+        const int b = (int)(item / chunks), chunk = (int)(item - (long)b * chunks);
+        double sd = (double)cfg_hi;
+        if (cfg_lo != cfg_hi) {
+            const double r = (double)t[b] / (double)tmax, hpi = 1.57079632679489661923;
+            const double rate = rate_kind == 1 ? cos((r - 1.0) * hpi) : rate_kind == 2 ? 1.0 - cos(r * hpi) : r;
+            sd = ((double)cfg_hi - (double)cfg_lo) * rate + (double)cfg_lo;
+        }
+        const float s = (float)sd;
+        const float w = sw ? sw[b] : 1.0f;
+        const float* u = pred2 + (size_t)b * per; const float* c = u + half; const float* y = target + (size_t)b * per;
+        const float* mb = mask ? mask + (size_t)b * mask_c * HW : nullptr;
+        float* gu = grad2 ? grad2 + (size_t)b * per : nullptr;
+        if (vec) {
+            for (long i = (long)chunk * blockDim.x + threadIdx.x; i < per / 4; i += (long)chunks * blockDim.x) {
+                const hcp_f32x4 uv = *(const hcp_f32x4*)(u + i * 4), cv = *(const hcp_f32x4*)(c + i * 4), yv = *(const hcp_f32x4*)(y + i * 4);
+                hcp_f32x4 mv = {1.f, 1.f, 1.f, 1.f};
+                if (mb) mv = *(const hcp_f32x4*)(mb + (mask_c == 1 ? (i * 4) % HW : i * 4));
+                hcp_f32x4 gn, gp;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const double dd = (double)uv[q] + sd * ((double)cv[q] - (double)uv[q]) - (double)yv[q];
+                    acc += dd * dd * ((double)mv[q] * (double)w);
+                    const float g = gs * (float)dd * (mv[q] * w);
+                    gn[q] = (1.0f - s) * g; gp[q] = s * g;
+                }
+                if (gu) { *(hcp_f32x4*)(gu + i * 4) = gn; *(hcp_f32x4*)(gu + half + i * 4) = gp; }
+            }
+        } else {
+            for (long i = (long)chunk * blockDim.x + threadIdx.x; i < per; i += (long)chunks * blockDim.x) {
+                const float m = mb ? mb[mask_c == 1 ? i % HW : i] : 1.0f;
+                const double dd = (double)u[i] + sd * ((double)c[i] - (double)u[i]) - (double)y[i];
+                acc += dd * dd * ((double)m * (double)w);
+                const float g = gs * (float)dd * (m * w);
+                if (gu) { gu[i] = (1.0f - s) * g; gu[half + i] = s * g; }
+            }
+        }
+    }
+    const double tot = cfg_block_sum(acc, (double*)smem);
+    if (threadIdx.x == 0) part[blockIdx.x] = (float)tot;
+}
+HCP_KERNEL(256) cfg_mse_finish_kernel(const float* part, int count, double scale, float* loss) {
+    HCP_DYN_SMEM(smem);
+    double acc = 0.0;
+    for (int k = threadIdx.x; k < count; k += 256) acc += (double)part[k];
+    const double tot = cfg_block_sum(acc, (double*)smem);
+    if (threadIdx.x == 0) *loss = (float)(tot * scale);
 }
 
 // dst[m, 0:C] = src[m, 0:C] with independent row strides (channel concat / split of channels-last tensors)
@@ -433,6 +510,33 @@ HCP_API int hcp_mse_masked_mean(const float* pred, const float* target, const fl
     HCP_LAUNCH(mse_kernel, dim3(pw_grid((long)B * C * HW)), dim3(PW_THREADS), 0, stream, pred, target, mask, mask_channels,
                sample_weight, loss, grad, B, C, HW, scale);
     HCP_LAUNCH_CHECK("mse_masked_mean");
+}
+
+// DreamArtist: loss = weight * mean((e - target)^2 * mask * sample_weight[b]) over B*C*HW with e_b = u_b + s_b (c_b - u_b), u / c = the
+// negative / positive half of pred2 [2B, C, HW]; s_b = (cfg_hi - cfg_lo) rate_b + cfg_lo from timesteps[b] (rate_kind 0 ln, 1 cos, 2 cos2;
+// cfg_lo == cfg_hi: a fixed scale, timesteps unused).  grad2 (optional, [2B, C, HW]) = d loss / d pred2.  partials: HCP_CFG_MSE_PARTIALS
+// floats of workspace — one per workgroup, added in index order by a second launch: no atomics, no memset, the same bits on every run.
+HCP_API int hcp_cfg_mse_masked_mean(const float* pred2, const float* target, const float* mask, int mask_channels,
+                                    const float* sample_weight, const long long* timesteps, float cfg_lo, float cfg_hi, int rate_kind,
+                                    int num_train_timesteps, float* loss, float* grad2, float* partials, int B, int C, int HW, float weight,
+                                    hipStream_t stream) {
+    HCP_REQUIRE(pred2 && target && loss && partials && B > 0 && C > 0 && HW > 0, "hcp_cfg_mse_masked_mean: bad arguments");
+    HCP_REQUIRE(!mask || mask_channels == 1 || mask_channels == C, "hcp_cfg_mse_masked_mean: mask channels must be 1 or C");
+    HCP_REQUIRE(cfg_lo == cfg_hi || (timesteps && num_train_timesteps > 1 && rate_kind >= 0 && rate_kind <= 2),
+                "hcp_cfg_mse_masked_mean: a dynamic scale needs timesteps, num_train_timesteps > 1 and rate_kind 0 (ln), 1 (cos) or 2 (cos2)");
+    const long per = (long)C * HW;
+    const int vec = HW % 4 == 0 && (((size_t)pred2 | (size_t)target | (size_t)mask | (size_t)grad2) & 15) == 0;
+    const long units = vec ? per / 4 : per;
+    long chunks = (units + PW_THREADS - 1) / PW_THREADS;
+    if (chunks > 2048) chunks = 2048;
+    long grid = (long)B * chunks;
+    if (grid > 2048) grid = 2048;                      // HCP_CFG_MSE_PARTIALS
+    const float scale = weight / (float)((long)B * per);
+    HCP_LAUNCH(cfg_mse_kernel, dim3((int)grid), dim3(PW_THREADS), 256 * sizeof(double), stream, pred2, target, mask, mask_channels, sample_weight,
+               timesteps, cfg_lo, cfg_hi, rate_kind, num_train_timesteps - 1, grad2, partials, B, C, HW, (int)chunks, vec, scale);
+    HCP_LAUNCH(cfg_mse_finish_kernel, dim3(1), dim3(256), 256 * sizeof(double), stream, (const float*)partials, (int)grid,
+               (double)weight / (double)((long)B * per), loss);
+    HCP_LAUNCH_CHECK("cfg_mse_masked_mean");
 }
 
 // dst[m, :C] = src[m, :C]; row strides sld/dld in elements (all multiples of 8). Used for the up-block skip concat

@@ -758,6 +758,47 @@ def mse_masked_mean(pred, target, mask=None, weight=1.0, want_grad=True, sample_
     return loss, grad
 
 
+CFG_RATE_KINDS = {"ln": 0, "cos": 1, "cos2": 2}
+CFG_MSE_PARTIALS = 2048        # include/hcp_mi355x.h HCP_CFG_MSE_PARTIALS
+_CFG_PARTIALS = {}
+
+
+def cfg_mse_masked_mean(pred2, target, t, cfg, mask=None, weight=1.0, sample_weight=None, want_grad=True, num_train_timesteps=1000,
+                        partials=None):
+    """DreamArtist loss (reference models/cfg_context.py:23-39): pred2 [2B, C, ...] = [negative rows ; positive rows], target [B, C, ...],
+    t int64 [B] (the RAW timesteps), cfg = (lo, hi, 'ln' | 'cos' | 'cos2').  Returns (weight * mean((e - target)^2 * mask *
+    sample_weight[b]) as a device scalar with e = u + s_b (c - u), d loss / d pred2 [2B, C, ...]).  Ordered partial sums: bit-reproducible.
+    partials: CFG_MSE_PARTIALS floats of workspace (default: one buffer per device, stream-ordered like every workspace here)."""
+    assert pred2.dtype == torch.float32 and target.dtype == torch.float32 and pred2.is_contiguous() and target.is_contiguous()
+    B, C = target.shape[0], target.shape[1]
+    assert pred2.shape[0] == 2 * B and pred2.shape[1:] == target.shape[1:], "pred2 holds the negative rows, then the positive rows, of target's batch"
+    HW = target.numel() // (B * C)
+    lo, hi, kind = cfg
+    if kind not in CFG_RATE_KINDS:
+        raise ValueError(f"cfg_scale rate {kind!r}: 'ln', 'cos' or 'cos2'")
+    if lo != hi:
+        assert t is not None and t.dtype == torch.int64 and t.numel() == B and t.is_contiguous()
+    loss = torch.empty((1,), dtype=torch.float32, device=pred2.device)
+    grad = torch.empty_like(pred2) if want_grad else None
+    mc = 0
+    if mask is not None:
+        mask = mask.to(torch.float32).contiguous()
+        mc = mask.shape[1]
+        assert mask.shape[0] == B and mask.numel() == B * mc * HW
+    if sample_weight is not None:
+        assert sample_weight.dtype == torch.float32 and sample_weight.numel() == B and sample_weight.is_contiguous()
+    if partials is None:
+        partials = _CFG_PARTIALS.get(pred2.device)
+        if partials is None:
+            partials = _CFG_PARTIALS[pred2.device] = torch.empty(CFG_MSE_PARTIALS, dtype=torch.float32, device=pred2.device)
+    assert partials.dtype == torch.float32 and partials.numel() >= CFG_MSE_PARTIALS and partials.device == pred2.device
+    _chk(lib().hcp_cfg_mse_masked_mean(_p(pred2), _p(target), _p(mask), mc, _p(sample_weight), _p(t), float(lo), float(hi),
+                                       CFG_RATE_KINDS[kind], int(num_train_timesteps), _p(loss), _p(grad), _p(partials), B, C, HW,
+                                       float(weight), _stream(pred2)),
+         "hcp_cfg_mse_masked_mean")
+    return loss, grad
+
+
 def split_hi_lo(src):
     """fp32 [M, C] -> bf16 [M, 2C] = (bf16(src) | bf16(src - bf16(src))): the split form of a rank-r intermediate (T_SPLIT)."""
     assert src.dtype == torch.float32 and src.dim() == 2 and src.is_contiguous() and src.shape[1] % 4 == 0

@@ -690,7 +690,7 @@ def make_lora(model, cfg_lora):
     """Restates make_hcpdiff's LoRA half (cfg_net_tools.py:108-123): wrap every matched layer, return
     ([param groups], PluginGroup, LoraBucket)."""
     named = dict(model.named_modules())
-    groups, blocks = [], {}
+    groups, blocks, made_blocks = [], {}, []
     for lora_id, item in enumerate(cfg_lora):
         item = dict(item)
         layers = item.pop("layers")
@@ -702,10 +702,11 @@ def make_lora(model, cfg_lora):
             made = cls.wrap_model(lora_id, named[layer_name], parent_block=named[parent_name], host_name=host_name, **item)
             for k, v in made.items():
                 path = f"{layer_name}.{k}" if k else layer_name
-                blocks[path] = v
+                blocks[path] = v              # (keyed as the reference keys its LoraGroup: a later item on the same host takes the key)
+                made_blocks.append(v)         # the bucket holds EVERY block, item by item: the 'p' and 'n' items of DreamArtist++ share hosts
                 v.requires_grad_(True)
                 v.train()
                 params.extend(v.parameters())
         groups.append({"params": params, "lr": lr} if lr is not None else {"params": params})   # no key: a torch optimizer's own default applies
-    bucket = LoraBucket(blocks.values()) if blocks else None
+    bucket = LoraBucket(made_blocks) if made_blocks else None
     return groups, PluginGroup(blocks), bucket

@@ -237,6 +237,22 @@ int hcp_snr_loss_weight(const long long* timesteps, const float* alphas_cumprod,
 int hcp_mse_masked_mean(const float* pred, const float* target, const float* mask, int mask_channels,
                         const float* sample_weight, float* loss, float* grad, int B, int C, int HW, float weight,
                         hcpStream_t stream);
+/* DreamArtist (reference models/cfg_context.py:12-39 + train_ac.py:506-515): the loss on the classifier-free-guidance combination of a
+ * negative and a positive pass, and the gradient of both, in one streaming pass.  pred2 fp32 [2B, C, HW]: the negative ("uncond") rows
+ * first, then the positive rows; target fp32 [B, C, HW]; mask (null, or 1 / C channels) and sample_weight (null or float[B]) as in
+ * hcp_mse_masked_mean.  Per sample s_b = (cfg_hi - cfg_lo) rate_b + cfg_lo with r = timesteps[b] / (num_train_timesteps - 1) and
+ * rate_b = r (rate_kind 0, 'ln'), cos((r - 1) pi / 2) (1, 'cos'), 1 - cos(r pi / 2) (2, 'cos2'); cfg_lo == cfg_hi is a fixed scale
+ * (timesteps may be null).  e_b = u_b + s_b (c_b - u_b);  *loss = weight * mean((e - target)^2 * mask * sample_weight[b]) over B*C*HW;
+ * grad2 (optional, [2B, C, HW]) = d loss / d pred2: with g = 2 weight / (B C HW) (e - target) mask sample_weight[b] the negative rows
+ * get (1 - s_b) g, the positive rows s_b g.  partials: HCP_CFG_MSE_PARTIALS floats of workspace, one per workgroup, added in index
+ * order by a second launch: no atomics, no memset, loss and gradient carry the same bits on every run.  The loss side (s_b, the
+ * differences, squares and sums) is computed in double and rounded to fp32 twice, in the partial and in *loss; grad2 is fp32 arithmetic.
+ * 16-byte loads and stores when HW % 4 == 0 and the buffers are 16-byte aligned, a scalar path otherwise. */
+#define HCP_CFG_MSE_PARTIALS 2048
+int hcp_cfg_mse_masked_mean(const float* pred2, const float* target, const float* mask, int mask_channels,
+                            const float* sample_weight, const long long* timesteps, float cfg_lo, float cfg_hi, int rate_kind,
+                            int num_train_timesteps, float* loss, float* grad2, float* partials, int B, int C, int HW, float weight,
+                            hcpStream_t stream);
 
 /* out[p,q] (+)= scale * sum_m L[m,p] R[m,q]  (fp32 atomics): the rank-r LoRA weight gradients
  * dW_down = alpha (dY W_up)^T x, dW_up = alpha dY^T (x W_down^T) (autograd of lora_base_patch.py:61-74). */
