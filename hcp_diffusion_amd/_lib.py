@@ -79,6 +79,10 @@ _PROTOTYPES = {
     # x, dy, stats, dgamma, dbeta, M, C, stream
     "hcp_layernorm_affine_grad": (I, [P, P, P, P, P, I, I, P]),
     "hcp_add_noise": (I, [P, P, P, P, P, I, L, P]),
+    # noise, fields (host array of pointers), field_elems (host array of longs), n_max, dims, n_active, discount, mode, partials, B, C, h, w, stream
+    "hcp_pyramid_noise_accum": (I, [P, P, P, I, P, P, c_double, I, P, I, I, I, I, P]),
+    # x0, noise, timesteps, alphas_cumprod, xt, partials, std_out, B, C, h, w, stream
+    "hcp_pyramid_noise_finish": (I, [P, P, P, P, P, P, P, I, I, I, I, P]),
     "hcp_cfg_ddim_step": (I, [P, P, P, L, I, F, F, F, P]),
     "hcp_snr_loss_weight": (I, [P, P, P, I, I, F, P]),
     "hcp_quick_gelu": (I, [P, P, P, L, P]),
@@ -153,7 +157,7 @@ TOOLS_SYMBOLS = tuple(_TOOLS_PROTOTYPES)
 TOOLS_LIB_PATH = Path(__file__).resolve().parent / "libhcp_mi355x_tools.so"
 
 
-ABI_VERSION = 6         # include/hcp_mi355x.h HCP_ABI_VERSION: bumped whenever an exported signature or descriptor layout changes
+ABI_VERSION = 7         # include/hcp_mi355x.h HCP_ABI_VERSION: bumped whenever an exported signature or descriptor layout changes
 
 
 class HcpError(RuntimeError):

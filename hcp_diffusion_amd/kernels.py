@@ -620,6 +620,61 @@ def add_noise(x0, noise, t, alphas_cumprod):
     return xt
 
 
+PYRAMID_MAX_LEVELS = 16        # include/hcp_mi355x.h HCP_PYRAMID_MAX_LEVELS
+PYRAMID_PARTIALS = 4096        # include/hcp_mi355x.h HCP_PYRAMID_PARTIALS
+PYRAMID_MODES = {"bilinear": 0, "nearest": 1}
+
+
+def pyramid_noise_workspace(device):
+    """The partial sums of one pyramid_noise_accum / pyramid_noise_finish pair: 2 * PYRAMID_PARTIALS doubles."""
+    return torch.empty(2 * PYRAMID_PARTIALS, dtype=torch.float64, device=device)
+
+
+def pyramid_noise_accum(noise, fields, dims, n_active, discount, resize_mode="bilinear", partials=None):
+    """noise fp32 [B,C,h,w] += resize(fields[i-1] -> (h, w)) * discount**i for i = 1..n_active, IN PLACE, in one launch (reference
+    noise/pyramid_noise.py:25-30).  fields: fp32 buffers; level i is read as [B,C,hn,wn] at the start of fields[i-1], which may be larger.
+    dims: device int32 [len(fields), 2] = (hn, wn); n_active: device int32 [1].  resize_mode: 'bilinear' | 'nearest' (or the ABI's mode
+    number).  Returns the partials workspace (sums of the result per workgroup), which pyramid_noise_finish reads."""
+    assert noise.dtype == torch.float32 and noise.dim() == 4 and noise.is_contiguous()
+    if isinstance(resize_mode, str):
+        if resize_mode not in PYRAMID_MODES:
+            raise ValueError(f"resize_mode {resize_mode!r}: 'bilinear' or 'nearest'")
+        resize_mode = PYRAMID_MODES[resize_mode]
+    B, C, h, w = noise.shape
+    n_max = len(fields)
+    assert n_max <= PYRAMID_MAX_LEVELS, f"at most {PYRAMID_MAX_LEVELS} level fields"
+    for f in fields:
+        assert f.dtype == torch.float32 and f.is_contiguous() and f.device == noise.device and f.numel() > 0
+    assert dims.dtype == torch.int32 and dims.is_contiguous() and dims.numel() >= 2 * n_max and dims.device == noise.device
+    assert n_active.dtype == torch.int32 and n_active.numel() == 1 and n_active.device == noise.device
+    if partials is None:
+        partials = pyramid_noise_workspace(noise.device)
+    assert partials.dtype == torch.float64 and partials.numel() >= 2 * PYRAMID_PARTIALS and partials.device == noise.device
+    ptrs = (ctypes.c_void_p * max(n_max, 1))(*[f.data_ptr() for f in fields])
+    caps = (ctypes.c_long * max(n_max, 1))(*[f.numel() for f in fields])
+    _chk(lib().hcp_pyramid_noise_accum(_p(noise), ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(caps, ctypes.c_void_p), n_max, _p(dims),
+                                       _p(n_active), float(discount), int(resize_mode), _p(partials), B, C, h, w, _stream(noise)),
+         "hcp_pyramid_noise_accum")
+    return partials
+
+
+def pyramid_noise_finish(x0, noise, t, alphas_cumprod, partials, std_out=None):
+    """(xt, std): std = noise.std() over the whole tensor from pyramid_noise_accum's partials (fixed order: the same bits on every run) and
+    xt = sqrt(acp[t]) x0 + sqrt(1 - acp[t]) noise / std.  noise keeps the unnormalised sum (pyramid_noise.py:28 against :31)."""
+    assert x0.dtype == torch.float32 and noise.dtype == torch.float32 and x0.is_contiguous() and noise.is_contiguous()
+    assert x0.shape == noise.shape and x0.dim() == 4
+    assert t.dtype == torch.int64 and t.numel() == x0.shape[0] and t.is_contiguous() and alphas_cumprod.dtype == torch.float32
+    assert partials.dtype == torch.float64 and partials.numel() >= 2 * PYRAMID_PARTIALS
+    xt = torch.empty_like(x0)
+    if std_out is None:
+        std_out = torch.empty(1, dtype=torch.float32, device=x0.device)
+    assert std_out.dtype == torch.float32 and std_out.numel() == 1
+    B, C, h, w = x0.shape
+    _chk(lib().hcp_pyramid_noise_finish(_p(x0), _p(noise), _p(t), _p(alphas_cumprod), _p(xt), _p(partials), _p(std_out), B, C, h, w,
+                                        _stream(x0)), "hcp_pyramid_noise_finish")
+    return xt, std_out
+
+
 def cfg_ddim_step(x, eps2, a_t, a_prev, guidance_scale=1.0, out=None):
     """One DDIM (eta = 0) step with classifier-free guidance: eps2 is the UNet output on [uncond ; cond] (2B rows) or on B rows."""
     assert x.dtype == torch.float32 and eps2.dtype == torch.float32 and x.is_contiguous() and eps2.is_contiguous()

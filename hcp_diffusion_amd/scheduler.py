@@ -2,7 +2,12 @@
 step uses — ``config.num_train_timesteps`` and ``add_noise`` (train_ac.py:437-447) — over the native kernel.
 
 ``add_noise(x0, noise, t) = sqrt(acp_t) x0 + sqrt(1 - acp_t) noise`` with the scaled-linear beta schedule of Stable Diffusion
-(constants as in the reference's loggers/preview/image_previewer.py:28)."""
+(constants as in the reference's loggers/preview/image_previewer.py:28).
+
+The reference's ``hcpdiff.noise`` wrappers around that object have native counterparts here: ``NativePyramidNoiseScheduler``
+(multi-resolution noise, two launches whatever the level count: csrc/noise.hip) and ``NativeZeroTerminalScheduler`` (betas rescaled to
+zero terminal SNR).  Both delegate every other attribute to the scheduler they wrap and compose in either order."""
+import random
 from types import SimpleNamespace
 
 import torch
@@ -26,15 +31,152 @@ class NativeDDPMScheduler:
                                   for i in range(num_train_timesteps)], dtype=torch.float32)
         else:
             raise NotImplementedError(f"beta_schedule {beta_schedule!r}: 'scaled_linear', 'linear' and 'squaredcos_cap_v2' exist")
-        self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)
+        self.betas = betas                                 # (diffusers' attribute names: the zero-terminal wrapper replaces all three)
+        self.alphas = 1.0 - betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
         self._acp_dev = {}
 
     def _acp(self, device):
         key = str(device)
-        if key not in self._acp_dev:
-            self._acp_dev[key] = self.alphas_cumprod.to(device)
-        return self._acp_dev[key]
+        hit = self._acp_dev.get(key)
+        if hit is None or hit[0] is not self.alphas_cumprod:       # (a wrapper replaced the table: the device copy follows)
+            hit = self._acp_dev[key] = (self.alphas_cumprod, self.alphas_cumprod.to(device=device, dtype=torch.float32))
+        return hit[1]
 
     def add_noise(self, original_samples, noise, timesteps):
         x0 = original_samples.float().contiguous()
         return K.add_noise(x0, noise.float().contiguous(), timesteps.long(), self._acp(x0.device)).to(original_samples.dtype)
+
+
+class NativeNoiseBase:
+    """A wrapper around a noise scheduler (the reference's noise/noise_base.py): attributes it does not define are the wrapped
+    scheduler's, for reading AND for writing — ``wrapper.alphas_cumprod = table`` reaches the scheduler that owns the table through any
+    number of wrappers, which is what lets the two wrappers below compose in either order."""
+
+    def __init__(self, base_scheduler):
+        object.__setattr__(self, "base_scheduler", base_scheduler)
+
+    def __getattr__(self, item):                           # (only called when normal lookup fails)
+        if item == "base_scheduler":
+            raise AttributeError(item)
+        return getattr(self.base_scheduler, item)
+
+    def __setattr__(self, key, value):
+        if key not in self.__dict__ and hasattr(self.base_scheduler, key):
+            setattr(self.base_scheduler, key, value)
+        else:
+            object.__setattr__(self, key, value)
+
+
+def _acp_on(scheduler, device):
+    """The alphas_cumprod table of any (wrapped) scheduler as fp32 on `device`."""
+    if hasattr(scheduler, "_acp"):
+        return scheduler._acp(device)
+    return scheduler.alphas_cumprod.to(device=device, dtype=torch.float32)
+
+
+def pyramid_level_bounds(h, w, level, step_size):
+    """[(hn, wn)] upper bounds of the level sizes: the reference's loop with the smallest ratio it can draw (r = step_size).  Every draw
+    has r >= step_size, so level i is never larger than bound i and the loop never runs longer than this list."""
+    out = []
+    for i in range(1, level):
+        r = step_size
+        wn, hn = max(1, int(w / (r ** i))), max(1, int(h / (r ** i)))
+        out.append((hn, wn))
+        if wn == 1 or hn == 1:
+            break
+    return out
+
+
+def pyramid_level_dims(h, w, level, step_size):
+    """[(hn, wn)] of one draw — the host side of pyramid_noise.py:25-30: one ``random.random()`` of the global module per level,
+    r = that * 2 + step_size, sizes max(1, int(. / r**i)), stop after the first level with a side of 1."""
+    out = []
+    for i in range(1, level):
+        r = random.random() * 2 + step_size
+        wn, hn = max(1, int(w / (r ** i))), max(1, int(h / (r ** i)))
+        out.append((hn, wn))
+        if wn == 1 or hn == 1:
+            break
+    return out
+
+
+def check_pyramid_args(level, discount, step_size, resize_mode):
+    if resize_mode not in K.PYRAMID_MODES:
+        raise ValueError(f"pyramid noise resize_mode {resize_mode!r}: 'bilinear' or 'nearest'")
+    if not (isinstance(level, int) and 1 <= level <= K.PYRAMID_MAX_LEVELS + 1):
+        raise ValueError(f"pyramid noise level {level!r}: an int in [1, {K.PYRAMID_MAX_LEVELS + 1}] (level - 1 fields, one launch holds "
+                         f"{K.PYRAMID_MAX_LEVELS})")
+    if not step_size > 0:
+        raise ValueError(f"pyramid noise step_size {step_size!r}: must be positive")
+    float(discount)
+
+
+class NativePyramidNoiseScheduler(NativeNoiseBase):
+    """PyramidNoiseScheduler (reference noise/pyramid_noise.py).  The host side of ``add_noise`` is the reference's loop (the global
+    ``random`` module decides the level sizes); the level fields are drawn on the device, and all levels are resized, scaled and added
+    by ONE launch, the std and the noisy latents by a second.
+
+    As in the reference, ``noise`` is modified IN PLACE and is left holding the UNNORMALISED sum — the reference's ``noise += ...``
+    writes into the caller's tensor, its ``noise = noise / noise.std()`` binds a new one — while the returned noisy latents are built
+    from the sum divided by its std.  train_ac.make_noise hands that caller's tensor to the loss as the eps target."""
+
+    def __init__(self, base_scheduler, level: int = 10, discount: float = 0.9, step_size: float = 2., resize_mode: str = 'bilinear'):
+        super().__init__(base_scheduler)
+        check_pyramid_args(level, discount, step_size, resize_mode)
+        object.__setattr__(self, "level", level)
+        object.__setattr__(self, "discount", discount)
+        object.__setattr__(self, "step_size", step_size)
+        object.__setattr__(self, "resize_mode", resize_mode)
+
+    def add_noise(self, original_samples, noise, timesteps, fields=None):
+        """fields: None (drawn here with torch.randn on noise's device) or a list of at least as many tensors as the draw has levels,
+        field i holding at least B*C*hn_i*wn_i values (tests inject their draws)."""
+        with torch.no_grad():
+            b, c, h, w = noise.shape
+            dims = pyramid_level_dims(h, w, self.level, self.step_size)
+            dev = noise.device
+            if fields is None:
+                fields = [torch.randn(b, c, hn, wn, device=dev, dtype=torch.float32) for hn, wn in dims]
+            if len(fields) < len(dims):
+                raise ValueError(f"pyramid noise: {len(dims)} levels drawn, {len(fields)} fields given")
+            fields = [f.to(device=dev, dtype=torch.float32).contiguous() for f in fields[:K.PYRAMID_MAX_LEVELS]]
+            for f, (hn, wn) in zip(fields, dims):
+                if f.numel() < b * c * hn * wn:
+                    raise ValueError(f"pyramid noise: a field of {f.numel()} values for a level of {b}x{c}x{hn}x{wn}")
+            table = torch.zeros(max(len(fields), 1), 2, dtype=torch.int32)
+            for i, d in enumerate(dims):
+                table[i, 0], table[i, 1] = d
+            work = noise if (noise.dtype == torch.float32 and noise.is_contiguous()) else noise.float().contiguous()
+            part = K.pyramid_noise_accum(work, fields, table.to(dev), torch.tensor([len(dims)], dtype=torch.int32).to(dev), self.discount,
+                                         self.resize_mode)
+            x0 = original_samples.float().contiguous()
+            xt, _ = K.pyramid_noise_finish(x0, work, timesteps.long().contiguous(), _acp_on(self.base_scheduler, dev), part)
+            if work is not noise:
+                noise.copy_(work)                          # the caller's tensor carries the sum, in its own dtype
+        return xt.to(original_samples.dtype)
+
+
+def rescale_zero_terminal_snr(betas):
+    """Algorithm 1 of Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed" (arXiv 2305.08891), in the fp32 torch
+    operations and the operation order of the reference's noise/zero_terminal.py:21-42, so that the table carries the same bits: shift
+    sqrt(alphas_cumprod) so that its last entry is 0, rescale so that its first entry is unchanged, and read the betas back."""
+    abar_sqrt = torch.cumprod(1.0 - betas, dim=0).sqrt()
+    first, last = abar_sqrt[0].clone(), abar_sqrt[-1].clone()
+    abar_sqrt -= last
+    abar_sqrt *= first / (first - last)
+    abar = abar_sqrt ** 2
+    alphas = torch.cat([abar[0:1], abar[1:] / abar[:-1]])
+    return 1 - alphas
+
+
+class NativeZeroTerminalScheduler(NativeNoiseBase):
+    """ZeroTerminalScheduler (reference noise/zero_terminal.py): replaces ``betas``, ``alphas`` and ``alphas_cumprod`` of the wrapped
+    scheduler by the zero-terminal-SNR rescaling; ``add_noise`` is the wrapped scheduler's, on the new table.  alphas_cumprod[-1] is 0:
+    anything that divides by it (the 'sample' loss, the SNR-weighted criteria, a DDIM-eps sampler) is not defined on this table."""
+
+    def __init__(self, base_scheduler):
+        super().__init__(base_scheduler)
+        base_scheduler.betas = rescale_zero_terminal_snr(base_scheduler.betas)
+        base_scheduler.alphas = 1.0 - base_scheduler.betas
+        base_scheduler.alphas_cumprod = torch.cumprod(base_scheduler.alphas, dim=0)

@@ -16,6 +16,7 @@ per-step ``loss.item()`` sync (train_ac.py:504) is deferred to whenever the call
 """
 import contextlib
 import math
+import random
 
 import torch
 
@@ -151,6 +152,25 @@ def parse_cfg_scale(cfg_scale):
     return lo, hi, kind
 
 
+def parse_noise_cfg(noise_cfg):
+    """NativeTrainer's `noise_cfg=` -> (None or the pyramid settings {level, discount, step_size, resize_mode}, zero_terminal flag)."""
+    if noise_cfg is None:
+        return None, False
+    from .scheduler import check_pyramid_args
+    cfg = dict(noise_cfg)
+    kind, zero_terminal = cfg.pop("type", None), bool(cfg.pop("zero_terminal", False))
+    if kind not in (None, "pyramid"):
+        raise ValueError(f"noise_cfg type {kind!r}: 'pyramid' (and / or zero_terminal=True)")
+    extra = set(cfg) - ({"level", "discount", "step_size", "resize_mode"} if kind else set())
+    if extra:
+        raise ValueError(f"noise_cfg takes no {sorted(extra)}" + ("" if kind else " without type='pyramid'"))
+    if kind is None:
+        return None, zero_terminal
+    pyr = {**dict(level=10, discount=0.9, step_size=2.0, resize_mode="bilinear"), **cfg}       # PyramidNoiseScheduler's defaults
+    check_pyramid_args(pyr["level"], pyr["discount"], pyr["step_size"], pyr["resize_mode"])
+    return pyr, zero_terminal
+
+
 FP32_WIRE = 10      # chunk ids >= 10: parameters the kernels read as fp32 (biases, norm affine) — never rounded on the wire
 
 
@@ -204,7 +224,7 @@ class NativeTrainer:
                  overlap_wgrad=False, grouped_wgrad=True, train_cfg=None, plugins=None, ema=None, loss_cfg=None, text_encoder=None,
                  lora_te_cfg=None, comm=None, shard_optimizer=None, gradient_accumulation_steps=1, loss_type="eps",
                  overlap_exchange=False, grad_wire="fp32", param_wire="fp32", pt_cfg=None, pt_words=None, pt_weight_decay=5e-4,
-                 optimizer=None, cfg_scale=None):
+                 optimizer=None, cfg_scale=None, noise_cfg=None):
         """lora_cfg: the reference's ``lora_unet`` list ({layers, rank, alpha, lr, ...}); train_cfg: its ``unet`` list
         ({layers, lr}) of host modules to fine-tune in full (DreamBooth.yaml:6-10 uses ``layers: ['']`` = everything);
         plugins: [(plugin module, lr)] — trainable hook plugins such as controlnet.ControlNetHipPlugin (make_plugin,
@@ -248,7 +268,24 @@ class NativeTrainer:
         (pn b) order, the text side of the batch (prompt_ids or encoder_hidden_states, attn_mask) carries 2B rows — the B negative prompts
         first, as pair_dataset.collate_fn stacks them (:141-142) —, and loss and top gradient come from one kernel on the [2B] prediction:
         e = u + s_b (c - u) against the B targets (K.cfg_mse_masked_mean; mask, Min-SNR weights and loss_weight / accum as without it).
-        added_cond_kwargs / plugin_input are refused with an active scale: the reference hands their B-row tensors to the 2B UNet call."""
+        added_cond_kwargs / plugin_input are refused with an active scale: the reference hands their B-row tensors to the 2B UNet call.
+        Noise — noise_cfg: None = today's step, bit for bit; {'type': 'pyramid', level, discount, step_size, resize_mode} = the reference's
+        noise.PyramidNoiseScheduler around the step's scheduler, and / or {'zero_terminal': True} = its noise.ZeroTerminalScheduler.
+        Pyramid noise: the level sizes are drawn on the host per step exactly as the reference draws them (the global ``random`` module) and
+        reach the kernels as device data; level i's field is always drawn at its upper bound [B, C, int(h / step_size**i), int(w /
+        step_size**i)] (one ``randn`` for all levels, in the graph), of which the kernel reads the leading B C hn wn values — one captured
+        graph serves every draw.  As in the reference the eps target is the UNNORMALISED pyramid sum, the noisy latents come from the sum
+        divided by its std.  Allowed under an active cfg_scale: the noise is made before the repeat.  Zero terminal SNR
+        (alphas_cumprod[T - 1] = 0) is refused with loss_type='sample' and with an SNR-weighted loss_cfg: both divide by it."""
+        self.noise_pyramid, self.noise_zero_terminal = parse_noise_cfg(noise_cfg)
+        if self.noise_zero_terminal:
+            if loss_type == "sample":
+                raise ValueError("noise_cfg zero_terminal with loss_type='sample': x0 is recovered by dividing by sqrt(alphas_cumprod[t]), which "
+                                 "is 0 at t = T - 1 on a zero-terminal-SNR table")
+            if loss_cfg is not None and loss_cfg.get("type", "mse") != "mse":
+                raise ValueError(f"noise_cfg zero_terminal with loss_cfg type {loss_cfg.get('type')!r}: the SNR-weighted criteria divide by "
+                                 "snr = acp / (1 - acp), which is 0 at t = T - 1 on a zero-terminal-SNR table")
+            # (an active cfg_scale reads no alphas_cumprod — its rates are functions of t / (T - 1) alone —, so it combines with this table)
         self.opt_cfg = _optimizer_cfg(optimizer)
         self.cfg_scale = parse_cfg_scale(cfg_scale)
         self.cfg_active = self.cfg_scale is not None and self.cfg_scale[1] != 1.0
@@ -348,6 +385,12 @@ class NativeTrainer:
                 raise ValueError(f"Unknown loss criterion {loss_cfg['type']}")
             self.loss_kind, self.loss_gamma = loss_cfg["type"], float(loss_cfg.get("gamma", 1.0))
         self.acp = ddpm_alphas_cumprod(num_train_timesteps, device=self.device)
+        if self.noise_zero_terminal:
+            from .scheduler import NativeDDPMScheduler, NativeZeroTerminalScheduler
+            self.acp = NativeZeroTerminalScheduler(NativeDDPMScheduler(num_train_timesteps)).alphas_cumprod.to(self.device)
+        # pyramid noise: per position in the step's data list one device table [n_active, (hn, wn) x PYRAMID_MAX_LEVELS] — static inputs of
+        # the captured step, filled on the host before every step —, and one workspace for the ordered partial sums
+        self._noise_tables, self._noise_idx, self._noise_ws, self._noise_staging = {}, None, None, {}
         self.num_train_timesteps = num_train_timesteps
         self.pg = process_group
         self._ctor_lr, self._scale_lr_factor = lr, scale_lr_factor
@@ -379,7 +422,68 @@ class NativeTrainer:
     def make_noise(self, latents):
         noise = torch.randn_like(latents)
         t = torch.randint(0, self.num_train_timesteps, (latents.shape[0],), device=latents.device).long()
-        return K.add_noise(latents, noise, t, self.acp), noise, t
+        if getattr(self, "noise_pyramid", None) is None:
+            return K.add_noise(latents, noise, t, self.acp), noise, t
+        # PyramidNoiseScheduler.add_noise (noise/pyramid_noise.py:23-32): `noise` leaves as the unnormalised sum (the eps target, as in the
+        # reference, whose `noise += ...` writes into train_ac.make_noise's tensor while `noise / noise.std()` is a new one)
+        pyr = self.noise_pyramid
+        idx = self._noise_idx
+        if idx is None:                                   # forward_backward called on its own (eager): this call's sizes are drawn here
+            idx = 0
+            self._fill_noise_table(0, latents.shape[2], latents.shape[3])
+        table = self._noise_table(idx)
+        fields = self._draw_noise_fields(latents.shape, latents.device)
+        if self._noise_ws is None:
+            self._noise_ws = K.pyramid_noise_workspace(latents.device)
+        K.pyramid_noise_accum(noise, fields, table[1:], table[:1], pyr["discount"], pyr["resize_mode"], self._noise_ws)
+        noisy, _ = K.pyramid_noise_finish(latents, noise, t, self.acp, self._noise_ws)
+        return noisy, noise, t
+
+    def _noise_table(self, idx):
+        if idx not in self._noise_tables:
+            self._noise_tables[idx] = torch.zeros(1 + 2 * K.PYRAMID_MAX_LEVELS, dtype=torch.int32, device=self.device)
+        return self._noise_tables[idx]
+
+    def _fill_noise_table(self, idx, h, w):
+        """One draw of the level sizes (the reference's host loop: one random.random() per level) into table `idx`; one small host-to-device
+        copy, outside any capture.  On the GPU the copy is asynchronous, from a ring of pinned staging buffers: a copy from pageable memory
+        returns only when the stream has drained, which would keep the host from enqueueing replay k + 1 while replay k runs.  Each slot
+        carries the event of its last copy, waited for before the slot is written again (only a host eight steps ahead ever waits)."""
+        from .scheduler import pyramid_level_dims
+        dims = pyramid_level_dims(h, w, self.noise_pyramid["level"], self.noise_pyramid["step_size"])
+        n = 1 + 2 * K.PYRAMID_MAX_LEVELS
+        table = self._noise_table(idx)
+        if table.is_cuda:
+            ring = self._noise_staging.setdefault(idx, [[], 0])
+            if len(ring[0]) < 8:
+                ring[0].append((torch.zeros(n, dtype=torch.int32).pin_memory(), torch.cuda.Event()))
+            host, done = ring[0][ring[1] % len(ring[0])]
+            ring[1] += 1
+            done.synchronize()
+        else:
+            host, done = torch.zeros(n, dtype=torch.int32), None
+        host.zero_()
+        host[0] = len(dims)
+        host[1:1 + 2 * len(dims)] = torch.tensor(dims, dtype=torch.int32).flatten()
+        table.copy_(host, non_blocking=True)
+        if done is not None:
+            done.record()
+        return dims
+
+    def _draw_noise_levels(self, data_list):
+        """Before a step runs or replays: the level sizes of every dataset's batch, in order."""
+        if getattr(self, "noise_pyramid", None) is not None:
+            for i, b in enumerate(data_list):
+                self._fill_noise_table(i, b["latents"].shape[2], b["latents"].shape[3])
+
+    def _draw_noise_fields(self, shape, device):
+        """The level fields at their upper bounds (every draw of the sizes fits: r >= step_size): ONE randn, cut into the levels."""
+        from .scheduler import pyramid_level_bounds
+        B, C, h, w = shape
+        bounds = pyramid_level_bounds(h, w, self.noise_pyramid["level"], self.noise_pyramid["step_size"])
+        sizes = [B * C * hn * wn for hn, wn in bounds]
+        flat = torch.randn(max(sum(sizes), 1), dtype=torch.float32, device=device)
+        return list(flat.split(sizes)) if sizes else []
 
     def forward_backward(self, latents, encoder_hidden_states, mask=None, added_cond_kwargs=None, plugin_input=None, prompt_ids=None,
                          attn_mask=None, exchange=False):
@@ -674,12 +778,14 @@ class NativeTrainer:
         for i, b in enumerate(data_list):
             lw = b.get("loss_weight", 1.0)
             keep, self.loss_weight = self.loss_weight, self.loss_weight * lw
+            self._noise_idx = i                    # (pyramid noise: this batch's level table)
             try:
                 l = self.forward_backward(b["latents"], b.get("encoder_hidden_states"), b.get("mask"), b.get("added_cond_kwargs"),
                                           b.get("plugin_input"), b.get("prompt_ids"), b.get("attn_mask"),
                                           exchange=exchange and i == len(data_list) - 1)
             finally:
                 self.loss_weight = keep
+                self._noise_idx = None
             total = l if total is None else total + l
         return total
 
@@ -702,6 +808,8 @@ class NativeTrainer:
         early = sync and self._overlap             # this backward sends the early chunks itself
         sent = ()
         if not self.use_graph:
+            if getattr(self, "noise_pyramid", None) is not None:
+                self._draw_noise_levels(data_list)
             self.loss = self._run_all(data_list, exchange=early)
             sent = tuple(sorted(self._sent))
         else:
@@ -722,6 +830,8 @@ class NativeTrainer:
                 live = dict(self._tensors(b))
                 for path, t in self._tensors(sb):
                     t.copy_(live[path])
+            if getattr(self, "noise_pyramid", None) is not None:
+                self._draw_noise_levels(data_list)     # the level tables are static inputs too: this step's sizes, drawn as eager mode draws them
             graph.replay()
             self.loss = loss
         if sync:
@@ -750,10 +860,11 @@ class NativeTrainer:
 
     def _snapshot(self):
         snap = [(st, [t.clone() for t in st.tensors()], st.bucket.params.clone(), st.bucket.grads.clone()) for st in self._states()]
-        return snap, torch.get_rng_state(), (torch.cuda.get_rng_state(self.device) if self.device.type == "cuda" else None)
+        return snap, torch.get_rng_state(), (torch.cuda.get_rng_state(self.device) if self.device.type == "cuda" else None), random.getstate()
 
     def _restore(self, saved):
-        snap, cpu_rng, dev_rng = saved
+        snap, cpu_rng, dev_rng, host_rng = saved
+        random.setstate(host_rng)                  # (pyramid noise draws its level sizes from the global `random` module)
         with torch.no_grad():
             for st, ts, p_, g_ in snap:
                 for t, v in zip(st.tensors(), ts):
@@ -777,7 +888,7 @@ class NativeTrainer:
         static = [clone(b) for b in data_list]
         # Warm-up on a side stream (allocator growth, lazy weight packing and autotuned workspaces must not happen inside the
         # capture).  It runs real steps, so every piece of training state it touches — parameters, gradients, AdamW moments,
-        # step counters, EMA, the RNG streams — is put back afterwards: the first captured step is the FIRST optimisation step,
+        # step counters, EMA, the RNG streams (torch's and the host `random` module's) — is put back afterwards: the first captured step is the FIRST optimisation step,
         # as in eager mode and as in the reference.
         saved = self._snapshot()
         side = torch.cuda.Stream()
@@ -788,6 +899,7 @@ class NativeTrainer:
         try:
             with torch.cuda.stream(side):
                 for _ in range(2):
+                    self._draw_noise_levels(static)
                     self._run_all(static, exchange=early)
                     self.all_reduce()
                     self.optimizer_step(**({"early_sent": tuple(sorted(self._sent))} if self._sent else {}))

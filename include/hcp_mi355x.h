@@ -31,8 +31,9 @@ int hcp_is_emulated(void); /* 0 for the product library */
  * residual stream: residual_lo / D_lo on hcp_gemm_bf16 / hcp_gemm_lora_bf16, x_lo / addend_lo / dx_lo on hcp_layernorm_fwd / _bwd; the
  * GEGLU-forward output gact on hcp_gemm_bf16 / hcp_gemm_lora_bf16.  4: prompt tuning — hcp_embedding_pt_fwd_bf16 /
  * hcp_embedding_pt_bwd_f32 (csrc/embedding.hip).  5: folded upsampler convs — hcp_conv_fold_pack / hcp_conv3x3_up_fold_bf16.
- * 6: SDXL's second text encoder — hcp_gelu, hcp_clip_pool_fwd / hcp_clip_pool_bwd. */
-#define HCP_ABI_VERSION 6
+ * 6: SDXL's second text encoder — hcp_gelu, hcp_clip_pool_fwd / hcp_clip_pool_bwd.  7: pyramid noise — hcp_pyramid_noise_accum /
+ * hcp_pyramid_noise_finish (csrc/noise.hip). */
+#define HCP_ABI_VERSION 7
 int hcp_abi_version(void);
 /* Device self-check of the fp32 atomic path (no reference counterpart: the reference's sums are torch's).  workgroups x 256 threads add
  * small integers into line[16] and into bucket[i * stride], i < nb (both cleared here first); exact expected values:
@@ -185,6 +186,27 @@ int hcp_timestep_embedding_f32(const float* values, void* emb, int B, int dim, f
 /* DDPMScheduler.add_noise as called by train_ac.py:447 */
 int hcp_add_noise(const float* x0, const float* noise, const long long* timesteps, const float* alphas_cumprod, float* xt,
                   int B, long per_sample, hcpStream_t stream);
+/* Pyramid (multi-resolution) noise, PyramidNoiseScheduler.add_noise (reference hcpdiff/noise/pyramid_noise.py:17-32), as two launches
+ * whatever the number of levels (csrc/noise.hip).
+ * hcp_pyramid_noise_accum: noise fp32 [B, C, h, w], IN PLACE: noise += resize(field_i -> (h, w)) * discount^i for i = 1 .. *n_active.
+ * fields: HOST array of n_max (<= HCP_PYRAMID_MAX_LEVELS) device pointers, field_elems: HOST array of the floats each buffer holds;
+ * level i is read as a contiguous [B, C, hn_i, wn_i] tensor at the start of its buffer, which may be larger.  dims: DEVICE int32
+ * [n_max][2] = (hn_i, wn_i) and n_active: DEVICE int32 — one captured graph serves every draw of the sizes; a table the buffers cannot
+ * serve (a size < 1, B C hn wn above field_elems[i], *n_active outside [0, n_max]) reads nothing and leaves NaN in noise.  mode 0:
+ * bilinear as F.interpolate(align_corners=False) — src = max((dst + 0.5) in/out - 0.5, 0), i0 = floor(src), i1 = min(i0 + 1, in - 1);
+ * mode 1: nearest, floor(dst in/out); any other mode is refused.  partials: 2 * HCP_PYRAMID_PARTIALS doubles of workspace: every
+ * workgroup leaves the sum and the sum of squares of its results (double, fixed order, no atomics: the same bits on every run).
+ * hcp_pyramid_noise_finish (same B, C, h, w): adds the partials in index order to std = the unbiased (N - 1) standard deviation over
+ * the whole tensor, as Tensor.std(), and writes xt = sqrt(acp[t_b]) x0 + sqrt(1 - acp[t_b]) noise / std.  noise stays the UNNORMALISED
+ * sum: the reference adds into the caller's tensor in place (:28) and normalises a new one (:31), so its loss target is the sum.
+ * std_out: null, or one device float that receives std. */
+#define HCP_PYRAMID_MAX_LEVELS 16
+#define HCP_PYRAMID_PARTIALS 4096
+int hcp_pyramid_noise_accum(float* noise, const float* const* fields, const long* field_elems, int n_max, const int* dims,
+                            const int* n_active, double discount, int mode, double* partials, int B, int C, int h, int w,
+                            hcpStream_t stream);
+int hcp_pyramid_noise_finish(const float* x0, const float* noise, const long long* timesteps, const float* alphas_cumprod, float* xt,
+                             const double* partials, float* std_out, int B, int C, int h, int w, hcpStream_t stream);
 /* --- VAE encode (AutoencoderKL.encode(...).latent_dist.sample() * scaling_factor, reference
  * data/pair_dataset.py:72-75 and train_ac.py:428-435).  The encoder reuses the conv / GroupNorm / GEMM entry points above; these
  * three finish it: the single-head d=512 mid-block attention runs as GEMM -> hcp_softmax_rows -> GEMM (V transposed by
