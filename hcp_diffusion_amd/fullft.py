@@ -138,3 +138,8 @@ class HostBucket:
             K.pack_weights(self._pieces, self._n_pieces, self._tiles)
         ops.invalidate_merged_cache()
         self._packed_ver = self._version()
+
+    refresh = repack                                    # (bucket protocol of NativeTrainer: refresh, named_tensors)
+
+    def named_tensors(self):
+        return list(self.named)

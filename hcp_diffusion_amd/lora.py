@@ -613,6 +613,11 @@ class LoraBucket:
         for b in self.blocks:                              # each factor's own counter too: an optimizer steps through the Parameters,
             b._pk_ver = (b.layer.W_down._version, b.layer.W_up._version)   # whose `.data` views do not share the bucket's version counter
 
+    refresh = pack                                         # (bucket protocol of NativeTrainer: refresh, named_tensors)
+
+    def named_tensors(self):
+        return [(f"lora_block[{i}].{n}", getattr(blk.layer, n)) for i, blk in enumerate(self.blocks) for n in ("W_down", "W_up")]
+
     def _stale(self, blocks):
         """Has anything written the fp32 factors since the bf16 operands were derived?  The flat buffer's counter sees in-place
         writes to `params` (NativeTrainer's fused kernel is followed by an explicit pack()); the factors' own counters see a

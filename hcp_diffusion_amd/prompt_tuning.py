@@ -168,5 +168,8 @@ class PTBucket:
                 if all(p is not q for q in hook.emb_train):
                     hook.emb_train.append(p)
 
-    def pack(self):                                           # (bucket protocol of NativeTrainer: the kernels read fp32 directly)
+    def refresh(self):                                        # (bucket protocol of NativeTrainer: the kernels read fp32 directly)
         pass
+
+    def named_tensors(self):
+        return list(zip(self.names, self.words))

@@ -112,6 +112,72 @@ def check_pyramid_args(level, discount, step_size, resize_mode):
     float(discount)
 
 
+class PyramidNoiseState:
+    """Pyramid noise inside NativeTrainer's step: the settings, per position in the step's data list one device table [n_active, (hn, wn)
+    x PYRAMID_MAX_LEVELS] — static inputs of the captured step, filled on the host before every step —, their pinned staging rings, the
+    workspace of the ordered partial sums, and `idx`: the table of the batch being run (None: forward_backward called on its own)."""
+
+    def __init__(self, settings, device):
+        self.level, self.discount, self.step_size, self.resize_mode = (settings[k] for k in ("level", "discount", "step_size", "resize_mode"))
+        self.device, self.tables, self.staging, self.ws, self.idx = device, {}, {}, None, None
+
+    def table(self, idx):
+        if idx not in self.tables:
+            self.tables[idx] = torch.zeros(1 + 2 * K.PYRAMID_MAX_LEVELS, dtype=torch.int32, device=self.device)
+        return self.tables[idx]
+
+    def fill(self, idx, h, w):
+        """One draw of the level sizes (the reference's host loop: one random.random() per level) into table `idx`; one small host-to-device
+        copy, outside any capture.  On the GPU the copy is asynchronous, from a ring of pinned staging buffers: a copy from pageable memory
+        returns only when the stream has drained, which would keep the host from enqueueing replay k + 1 while replay k runs.  Each slot
+        carries the event of its last copy, waited for before the slot is written again (only a host eight steps ahead ever waits)."""
+        dims = pyramid_level_dims(h, w, self.level, self.step_size)
+        n = 1 + 2 * K.PYRAMID_MAX_LEVELS
+        table = self.table(idx)
+        if table.is_cuda:
+            ring = self.staging.setdefault(idx, [[], 0])
+            if len(ring[0]) < 8:
+                ring[0].append((torch.zeros(n, dtype=torch.int32).pin_memory(), torch.cuda.Event()))
+            host, done = ring[0][ring[1] % len(ring[0])]
+            ring[1] += 1
+            done.synchronize()
+        else:
+            host, done = torch.zeros(n, dtype=torch.int32), None
+        host.zero_()
+        host[0] = len(dims)
+        host[1:1 + 2 * len(dims)] = torch.tensor(dims, dtype=torch.int32).flatten()
+        table.copy_(host, non_blocking=True)
+        if done is not None:
+            done.record()
+        return dims
+
+    def draw_levels(self, data_list):
+        """Before a step runs or replays: the level sizes of every dataset's batch, in order."""
+        for i, b in enumerate(data_list):
+            self.fill(i, b["latents"].shape[2], b["latents"].shape[3])
+
+    def draw_fields(self, shape, device):
+        """The level fields at their upper bounds (every draw of the sizes fits: r >= step_size): ONE randn, cut into the levels."""
+        B, C, h, w = shape
+        sizes = [B * C * hn * wn for hn, wn in pyramid_level_bounds(h, w, self.level, self.step_size)]
+        flat = torch.randn(max(sum(sizes), 1), dtype=torch.float32, device=device)
+        return list(flat.split(sizes)) if sizes else []
+
+    def add_noise(self, latents, noise, t, acp):
+        """PyramidNoiseScheduler.add_noise (noise/pyramid_noise.py:23-32): `noise` leaves as the unnormalised sum (the eps target, as in the
+        reference, whose `noise += ...` writes into train_ac.make_noise's tensor while `noise / noise.std()` is a new one)."""
+        idx = self.idx
+        if idx is None:                                   # forward_backward called on its own (eager): this call's sizes are drawn here
+            idx = 0
+            self.fill(0, latents.shape[2], latents.shape[3])
+        table = self.table(idx)
+        fields = self.draw_fields(latents.shape, latents.device)
+        if self.ws is None:
+            self.ws = K.pyramid_noise_workspace(latents.device)
+        K.pyramid_noise_accum(noise, fields, table[1:], table[:1], self.discount, self.resize_mode, self.ws)
+        return K.pyramid_noise_finish(latents, noise, t, acp, self.ws)[0]
+
+
 class NativePyramidNoiseScheduler(NativeNoiseBase):
     """PyramidNoiseScheduler (reference noise/pyramid_noise.py).  The host side of ``add_noise`` is the reference's loop (the global
     ``random`` module decides the level sizes); the level fields are drawn on the device, and all levels are resized, scaled and added

@@ -448,7 +448,7 @@ def test_graph_cfg_step_equals_eager():
         _fix_noise(tr, dev, noise, t)
         grads, losses = [], []
         for step in range(3):
-            tr.optimizer_step = lambda: None
+            tr.optimizer_step = lambda *a, **k: None
             tr._opt_graph = None
             loss = tr.train_one_step(b["latents"], b["encoder_hidden_states"])
             torch.cuda.synchronize()

@@ -686,7 +686,7 @@ def test_two_dataset_step_accumulates_like_reference(backend):
     expect = grads[0] + 0.5 * grads[1]
     seq = iter([0, 1])
     tr.make_noise = lambda lat: (lambda i: (K.add_noise(lat, n[i], t[i], tr.acp), n[i], t[i]))(next(seq))
-    tr.optimizer_step = lambda: None                              # look at the accumulated gradient before it is consumed
+    tr.optimizer_step = lambda *a, **k: None                              # look at the accumulated gradient before it is consumed
     loss = tr.train_data_list([dict(latents=x[0], encoder_hidden_states=e[0]),
                                dict(latents=x[1], encoder_hidden_states=e[1], loss_weight=0.5)])
     assert loss.numel() == 1

@@ -373,7 +373,7 @@ def test_trainer_pyramid_step_vs_float64_noise(backend, monkeypatch):
     assert bounds == [(4, 4), (2, 2), (1, 1)]
     g = torch.Generator().manual_seed(21)
     fields = [torch.randn(B * C * hn * wn, generator=g) for hn, wn in bounds]          # drawn at the upper bounds, as the step draws them
-    tr._draw_noise_fields = lambda shape, device: [f.to(device) for f in fields]
+    tr._pyramid.draw_fields = lambda shape, device: [f.to(device) for f in fields]
     tr.optimizer_step = lambda *a, **k: None                                            # (keeps the bucket gradients)
     seen, targets = [], []
     real_make, real_mse = tr.make_noise, K.mse_masked_mean
@@ -390,8 +390,8 @@ def test_trainer_pyramid_step_vs_float64_noise(backend, monkeypatch):
     torch.manual_seed(31)
     n0 = torch.randn_like(b["latents"])
     t = torch.randint(0, 1000, (B,), device=dev).long()
-    assert 1 <= len(dims) <= len(bounds) and int(tr._noise_tables[0][0]) == len(dims)
-    assert tr._noise_tables[0][1:1 + 2 * len(dims)].cpu().tolist() == [v for d in dims for v in d]
+    assert 1 <= len(dims) <= len(bounds) and int(tr._pyramid.tables[0][0]) == len(dims)
+    assert tr._pyramid.tables[0][1:1 + 2 * len(dims)].cpu().tolist() == [v for d in dims for v in d]
     noisy, noise, t_step = seen[0]
     assert torch.equal(t_step, t) and targets[0] is noise
     xt64, s64, sd64 = noise_ref.pyramid_add_noise(b["latents"].cpu(), n0.cpu(), fields, dims, 0.9, "bilinear", t.cpu(), tr.acp.cpu())
@@ -422,7 +422,7 @@ def test_accumulation_ema_lion_two_datasets_and_cfg_run_under_it(backend):
     random.seed(1)
     loss = tr.train_data_list(data)
     assert torch.isfinite(loss).all() and torch.equal(tr.bucket.params, p0) and tr.bucket.grads.abs().max().item() > 0
-    assert sorted(tr._noise_tables) == [0, 1]
+    assert sorted(tr._pyramid.tables) == [0, 1]
     loss = tr.train_data_list(data)
     assert torch.isfinite(loss).all() and not torch.equal(tr.bucket.params, p0) and tr.bucket.grads.abs().max().item() == 0.0
     assert not torch.equal(tr._lora_state.ema, p0)
@@ -468,7 +468,7 @@ def test_warm_up_restore_puts_back_the_host_random_state(backend):
     random.seed(5)
     state = random.getstate()
     saved = tr._snapshot()
-    tr._draw_noise_levels([_batch(backend.device)])
+    tr._pyramid.draw_levels([_batch(backend.device)])
     assert random.getstate() != state
     tr._restore(saved)
     assert random.getstate() == state
@@ -511,7 +511,7 @@ def test_graph_pyramid_step_equals_eager():
         losses, seen = [], []
         for step in range(GRAPH_STEPS):
             losses.append(tr.train_one_step(b["latents"], b["encoder_hidden_states"], mask=mask).clone())
-            seen.append(int(tr._noise_tables[0][0]))
+            seen.append(int(tr._pyramid.tables[0][0]))
         torch.cuda.synchronize()
         assert seen == counts
         if use_graph:

@@ -361,8 +361,7 @@ TRAINER_OPTS = {"adafactor": {"type": "adafactor", "lr": None, "relative_step": 
 
 
 def _bucket_named(tr, st):
-    from hcp_diffusion_amd.trainer import _bucket_tensors
-    return _bucket_tensors(st.bucket)
+    return st.bucket.named_tensors()
 
 
 @pytest.mark.parametrize("which", list(TRAINER_OPTS))

@@ -144,7 +144,7 @@ def test_graph_capture_does_not_perturb_training_state():
         for _ in range(2):
             tr.train_one_step(b["latents"], b["encoder_hidden_states"])
         torch.cuda.synchronize()
-        outs.append((tr.bucket.params.clone(), tr.exp_avg.clone(), tr.step_count.item(), tr._lora_state.ema.clone(), torch.rand(1, device=dev).item()))
+        outs.append((tr.bucket.params.clone(), tr._lora_state.exp_avg.clone(), tr._lora_state.step_count.item(), tr._lora_state.ema.clone(), torch.rand(1, device=dev).item()))
     (pe, me, se, ee, re_), (pg, mg, sg, eg, rg) = outs
     assert se == sg == 2
     assert ((pe - pg).abs().max() / pe.abs().max()).item() < 1e-5 and ((me - mg).abs().max() / me.abs().max()).item() < 1e-4
@@ -165,7 +165,7 @@ def test_graph_two_datasets_equal_eager(grouped):
         _fix_noise(tr, dev)
         tr.optimizer_step_real, grads = tr.optimizer_step, []
         for step in range(3):
-            tr.optimizer_step = lambda: None
+            tr.optimizer_step = lambda *a, **k: None
             tr._opt_graph = None
             tr.train_data_list([dict(d) for d in data])
             torch.cuda.synchronize()
@@ -490,7 +490,7 @@ def test_bf16_param_wire_routes_only_hip_layer_weights_and_the_stale_flag_follow
     calls = []
     st = types.SimpleNamespace(shard=True, pwire=torch.zeros(1))
     fake = types.SimpleNamespace(_micro=0, accum=1, _overlap=False, use_graph=False, _sent=set(), _opt_graph=types.SimpleNamespace(replay=lambda: calls.append("replay")),
-                                 _opt_graph_sent=(), _masters_stale=False, _states=lambda: [st], all_reduce=lambda: None,
+                                 _opt_graph_sent=(), _masters_stale=False, pt_bucket=None, cfg_active=False, _pyramid=None, _states=lambda: [st], all_reduce=lambda: None,
                                  _run_all=lambda data_list, exchange=False: torch.zeros(1), optimizer_step=lambda **kw: calls.append("eager"))
     T.NativeTrainer.train_data_list(fake, [dict(latents=torch.zeros(1, 4, 8, 8))])
     assert calls == ["replay"] and fake._masters_stale is True

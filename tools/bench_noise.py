@@ -95,8 +95,8 @@ def main():
     torch.cuda.synchronize()
     times = {name: [] for name in legs}
     losses, levels = {}, set()
-    fill = legs["pyramid"]._fill_noise_table                  # (host side: which level counts the timed steps drew)
-    legs["pyramid"]._fill_noise_table = lambda *a: (lambda dims: (levels.add(len(dims)), dims)[1])(fill(*a))
+    fill = legs["pyramid"]._pyramid.fill                  # (host side: which level counts the timed steps drew)
+    legs["pyramid"]._pyramid.fill = lambda *a: (lambda dims: (levels.add(len(dims)), dims)[1])(fill(*a))
     for _ in range(args.rounds):                              # alternate the two legs: whatever else the host does hits both
         for name, tr in legs.items():
             torch.cuda.synchronize()

@@ -50,7 +50,7 @@ if mode == "trainer":
     for i in range(steps):
         loss = tr.train_one_step(latents, ehs)
         torch.cuda.synchronize()
-        ok = (fin(loss), fin(tr.bucket.params), fin(tr.exp_avg))
+        ok = (fin(loss), fin(tr.bucket.params), fin(tr._lora_state.exp_avg))
         print(f"step {i}: loss {loss.item():.5f} finite(loss, params, exp_avg) {ok}", flush=True)
         if not all(ok):
             break
