@@ -92,7 +92,8 @@ def atomics_selfcheck(device, workgroups=2048, nb=4099, stride=37):
 
 # tools/trace_gemm_launches.py / tests/test_gemm_launches.py: a list collects one plain dict per GEMM-family launch — sizes, strides and
 # epilogue flags, enough to rebuild the call at its real shape (tests/gemm_check.py); tools/trace_attention_launches.py /
-# tests/test_attention_launches.py: the same for attention_fwd / attention_bwd (tests/attn_check.py).  None (the default): nothing is recorded.
+# tests/test_attention_launches.py: the same for attention_fwd / attention_bwd (tests/attn_check.py); tools/trace_lora_launches.py /
+# tests/test_lora_launches.py: lora_wgrad / lora_wgrad_pair / lora_wgrad_grouped (tests/lora_check.py).  None (the default): nothing is recorded.
 LAUNCHES = None
 
 
@@ -873,6 +874,9 @@ def lora_wgrad(L, R, out, P, scale, transpose_out, out_col0=0, lo=0):
     assert out_col0 == 0 or transpose_out
     ldo = out.shape[1]
     ptr = ctypes.c_void_p(out.data_ptr() + 4 * out_col0)
+    if LAUNCHES is not None:
+        _launch("lora_wgrad", M=M, Q=Q, r=int(P), ldl=L.stride(0), lo=int(lo), ldr=R.stride(0), ldo=ldo, transpose_out=bool(transpose_out),
+                out_col0=int(out_col0), scale=float(scale))
     ws = _workspace(L)
     _chk(lib().hcp_lora_wgrad(_p(L), L.stride(0), int(lo), _p(R), R.stride(0), ptr, ldo, M, P, Q, float(scale),
                               1 if transpose_out else 0, _p(ws), ws.numel(), _stream(L)), "hcp_lora_wgrad")
@@ -884,9 +888,28 @@ def lora_wgrad_pair(U, x, grad_down, T, dy, grad_up, r, scale):
     N = dy.shape[1]
     assert U.shape in ((M, 32), (M, 64)) and T.shape in ((M, 32), (M, 64)) and U.is_contiguous() and T.is_contiguous()      # 64: split (hi | lo)
     assert grad_down.shape == (r, Kd) and grad_up.shape == (N, r) and grad_down.is_contiguous() and grad_up.is_contiguous()
+    if LAUNCHES is not None:
+        _launch("lora_wgrad_pair", M=M, K=Kd, N=N, r=int(r), ldx=x.stride(0), ldy=dy.stride(0), ldu=U.shape[1], ldt=T.shape[1], scale=float(scale))
     ws = _workspace(x)
     _chk(lib().hcp_lora_wgrad_pair(_p(U), U.shape[1], _p(x), x.stride(0), Kd, _p(grad_down), _p(T), T.shape[1], _p(dy), dy.stride(0), N,
                                    _p(grad_up), M, r, float(scale), _p(ws), ws.numel(), _stream(x)), "hcp_lora_wgrad_pair")
+
+
+def _check_wgrad_item(i, item):
+    """What hcp_lora_wgrad / hcp_lora_wgrad_pair refuse, for layer i of a grouped call: the grouped kernel relies on the same (8-wide loads
+    of x / dy rows, whole 4-runs of q in the vector reduce, 32 rank slots) and its entry point cannot see the device-side table."""
+    (U, x, gd, T, dy, gu, r, scale) = item[:8]
+    slot0 = item[8] if len(item) > 8 else 0
+    M, Kd = x.shape
+    N = dy.shape[1]
+    assert Kd % 8 == 0 and N % 8 == 0, f"lora_wgrad_grouped: layer {i}: K ({Kd}) and N ({N}) must be multiples of 8"
+    assert x.stride(0) % 8 == 0 and dy.stride(0) % 8 == 0 and x.stride(1) == 1 and dy.stride(1) == 1, \
+        f"lora_wgrad_grouped: layer {i}: row strides of x ({x.stride(0)}) and dy ({dy.stride(0)}) must be multiples of 8"
+    assert 1 <= r <= 32, f"lora_wgrad_grouped: layer {i}: rank {r} outside 1..32"
+    assert slot0 >= 0 and slot0 + r <= 32, f"lora_wgrad_grouped: layer {i}: rank slots [{slot0}, {slot0 + r}) leave the 32 columns of U / T"
+    for g, shape, name in ((gd, (r, Kd), "grad_down"), (gu, (N, r), "grad_up")):
+        assert g.dtype == torch.float32 and tuple(g.shape) == shape and g.is_contiguous(), \
+            f"lora_wgrad_grouped: layer {i}: {name} must be contiguous fp32 of shape {shape}, got {g.dtype} {tuple(g.shape)} strides {g.stride()}"
 
 
 def lora_wgrad_grouped(items):
@@ -896,14 +919,20 @@ def lora_wgrad_grouped(items):
     u_lo / t_lo = column offset of the residual half of a split U / T (t_lo(.)), 0 = none.
     A gradient tensor named twice (a layer that ran twice in the forward) is taken by a second call on the same stream: inside one
     call the reduce adds into the bucket without atomics."""
+    for i, item in enumerate(items):              # before anything is bound, allocated or launched
+        _check_wgrad_item(i, item)
+    return _lora_wgrad_grouped_passes(items)
+
+
+def _lora_wgrad_grouped_passes(items):
     seen, first, rest = set(), [], []
     for item in items:
         key = (item[2].data_ptr(), item[5].data_ptr())
         (rest if key in seen else first).append(item)
         seen.add(key)
     if rest:
-        a = lora_wgrad_grouped(first)
-        b = lora_wgrad_grouped(rest)
+        a = _lora_wgrad_grouped_passes(first)
+        b = _lora_wgrad_grouped_passes(rest)
         return a + b
     import struct
     L = lib()
@@ -932,6 +961,16 @@ def lora_wgrad_grouped(items):
         if units * 512 <= ws.numel() or target <= 1:      # the slabs fit the workspace (a large model at a large batch: fewer token ranges per layer)
             break
         target //= 2
+    if LAUNCHES is not None:
+        layers = []
+        for item in items:
+            (U, x, gd, T, dy, gu, r, scale) = item[:8]
+            L.hcp_lora_wgrad_group_geometry(x.shape[0], x.shape[1], dy.shape[1], r, target, ctypes.byref(qt0), ctypes.byref(qt1), ctypes.byref(sp),
+                                            ctypes.byref(rows))
+            layers.append(dict(M=x.shape[0], K=x.shape[1], N=dy.shape[1], r=int(r), slot0=int(item[8]) if len(item) > 8 else 0, splits=sp.value,
+                               ldx=x.stride(0), ldy=dy.stride(0), ldu=U.stride(0), ldt=T.stride(0),
+                               u_lo=int(item[9]) if len(item) > 10 else 0, t_lo=int(item[10]) if len(item) > 10 else 0, scale=float(scale)))
+        _launch("lora_wgrad_grouped", layers=layers, target=target)
     dev = items[0][1].device
     src = torch.frombuffer(buf, dtype=torch.uint8)
     if dev.type == "cuda":

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 import attn_check as AC
 import gemm_check as GC
+import lora_check as LC
 import norm_check as NC
 from hcp_diffusion_amd import kernels as K
 
@@ -853,20 +854,25 @@ def test_lora_wgrad_and_pack(backend, M, Kd, N, r, split, monkeypatch):
         assert relerr(t_full(T2), t32) < 1e-4 and relerr(t_full(U2), u32) < 1e-4
         gds = torch.zeros(r, Kd, device=dev); gus = torch.zeros(N, r, device=dev)
         K.lora_wgrad_pair(U2, to(x), gds, T2, to(dy), gus, r, alpha)
+        LC.check_call([(U2, to(x), gds, T2, to(dy), gus, r, alpha, 0, 32, 32)], None, f"lora_wgrad_pair, split, {(M, Kd, N, r)}")
         gd32 = alpha * u32[:, :r].T @ x.float(); gu32 = alpha * dy.float().T @ t32[:, :r]
         assert relerr(gds, gd32) < 2e-4 and relerr(gus, gu32) < 2e-4
         gd1 = torch.zeros(r, Kd, device=dev); gu1 = torch.zeros(N, r, device=dev)
         K.lora_wgrad(U2, to(x), gd1, r, alpha, False, lo=K.t_lo(U2)); K.lora_wgrad(T2, to(dy), gu1, r, alpha, True, lo=K.t_lo(T2))
+        LC.check_call([(U2, to(x), gd1, T2, to(dy), gu1, r, alpha, 0, 32, 32)], None, f"lora_wgrad twice, split, {(M, Kd, N, r)}")
         assert relerr(gd1, gd32) < 2e-4 and relerr(gu1, gu32) < 2e-4
         keep = K.lora_wgrad_grouped([(U2, to(x), gds.zero_(), T2, to(dy), gus.zero_(), r, alpha, 0, 32, 32)])
+        LC.check_call([(U2, to(x), gds, T2, to(dy), gus, r, alpha, 0, 32, 32)], None, f"lora_wgrad_grouped, split, {(M, Kd, N, r)}")
         assert relerr(gds, gd32) < 2e-4 and relerr(gus, gu32) < 2e-4
         del keep
     gd = torch.zeros(r, Kd, device=dev); gu = torch.zeros(N, r, device=dev)
     K.lora_wgrad(U, to(x), gd, r, alpha, False)
     K.lora_wgrad(T, to(dy), gu, r, alpha, True)
+    LC.check_call([(U, to(x), gd, T, to(dy), gu, r, alpha)], None, f"lora_wgrad twice, {(M, Kd, N, r)}")
     assert relerr(gd, wdr.grad) < 2e-2 and relerr(gu, wur.grad) < 2e-2
     gd2 = torch.zeros(r, Kd, device=dev); gu2 = torch.zeros(N, r, device=dev)
     K.lora_wgrad_pair(U, to(x), gd2, T, to(dy), gu2, r, alpha)           # both gradients, one launch
+    LC.check_call([(U, to(x), gd2, T, to(dy), gu2, r, alpha)], None, f"lora_wgrad_pair, {(M, Kd, N, r)}")
     assert relerr(gd2, wdr.grad) < 2e-2 and relerr(gu2, wur.grad) < 2e-2
 
 
@@ -964,6 +970,7 @@ def test_lora_wgrad_grouped(backend):
     keep = K.lora_wgrad_grouped(items)
     for it, (rd, ru) in zip(items, refs):
         assert relerr(it[2], rd) < 2e-2 and relerr(it[5], ru) < 2e-2
+    LC.check_call(items, None, "lora_wgrad_grouped, three layers")
     del keep
 
 
@@ -986,6 +993,8 @@ def test_lora_wgrad_slabs_are_ordered_sums_without_atomics(backend, M, Kd, N, r,
         gd = torch.full((r, Kd), 0.25, device=dev); gu = torch.full((N, r), -0.5, device=dev)
         keep = K.lora_wgrad_grouped([(to(U), to(x), gd, to(T), to(dy), gu, r, 0.5, slot0)])
         assert relerr(gd - 0.25, rd) < 2e-2 and relerr(gu + 0.5, ru) < 2e-2
+        LC.check_call([(to(U), to(x), gd, to(T), to(dy), gu, r, 0.5, slot0)], [(torch.full_like(gd, 0.25), torch.full_like(gu, -0.5))],
+                      f"lora_wgrad_grouped {(M, Kd, N, r, slot0)}")
         runs.append((gd.cpu().clone(), gu.cpu().clone()))
         del keep
     assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
@@ -993,9 +1002,13 @@ def test_lora_wgrad_slabs_are_ordered_sums_without_atomics(backend, M, Kd, N, r,
         gd = torch.full((r, Kd), 0.25, device=dev); gu = torch.full((N, r), -0.5, device=dev)
         K.lora_wgrad_pair(to(U), to(x), gd, to(T), to(dy), gu, r, 0.5)
         assert relerr(gd - 0.25, rd) < 2e-2 and relerr(gu + 0.5, ru) < 2e-2
+        LC.check_call([(to(U), to(x), gd, to(T), to(dy), gu, r, 0.5)], [(torch.full_like(gd, 0.25), torch.full_like(gu, -0.5))],
+                      f"lora_wgrad_pair {(M, Kd, N, r)}")
         gd1 = torch.full((r, Kd), 0.25, device=dev); gu1 = torch.full((N, r), -0.5, device=dev)
         K.lora_wgrad(to(U), to(x), gd1, r, 0.5, False); K.lora_wgrad(to(T), to(dy), gu1, r, 0.5, True)
         assert relerr(gd1 - 0.25, rd) < 2e-2 and relerr(gu1 + 0.5, ru) < 2e-2
+        LC.check_call([(to(U), to(x), gd1, to(T), to(dy), gu1, r, 0.5)], [(torch.full_like(gd1, 0.25), torch.full_like(gu1, -0.5))],
+                      f"lora_wgrad twice {(M, Kd, N, r)}")
 
 
 def test_lora_wgrad_grouped_fits_its_slabs_to_the_workspace(backend, monkeypatch):
@@ -1013,6 +1026,7 @@ def test_lora_wgrad_grouped_fits_its_slabs_to_the_workspace(backend, monkeypatch
     gd = torch.zeros(r, Kd, device=dev); gu = torch.zeros(N, r, device=dev)
     keep = K.lora_wgrad_grouped([(to(U), to(x), gd, to(T), to(dy), gu, r, 1.0)])
     assert relerr(gd, rd) < 2e-2 and relerr(gu, ru) < 2e-2
+    LC.check_call([(to(U), to(x), gd, to(T), to(dy), gu, r, 1.0)], None, "lora_wgrad_grouped with a 40 KiB workspace")
     del keep
 
 
@@ -1031,6 +1045,7 @@ def test_lora_wgrad_grouped_takes_a_gradient_named_twice_in_two_passes(backend):
         rd = rd + U.float()[:, :r].T @ x.float(); ru = ru + dy.float().T @ T.float()[:, :r]
     keep = K.lora_wgrad_grouped(items)
     assert relerr(gd, rd) < 2e-2 and relerr(gu, ru) < 2e-2
+    LC.check_call(items, None, "lora_wgrad_grouped, one gradient pair named twice")
     del keep
 
 
