@@ -51,6 +51,10 @@ _PROTOTYPES = {
     "hcp_geglu_fwd": (I, [P, P, L, I, P]),
     "hcp_geglu_bwd": (I, [P, P, P, L, I, P]),
     "hcp_add_bf16": (I, [P, P, P, L, P]),
+    # y, residual, out, n, state, layer_id, group_base, p, stream / dy, dx, n, state, layer_id, group_base, p, stream / state, stream
+    "hcp_dropout_residual_fwd": (I, [P, P, P, L, P, ctypes.c_uint, ctypes.c_ulonglong, c_double, P]),
+    "hcp_dropout_bwd": (I, [P, P, L, P, ctypes.c_uint, ctypes.c_ulonglong, c_double, P]),
+    "hcp_dropout_advance": (I, [P, P]),
     "hcp_copy2d_bf16": (I, [P, I, P, I, L, I, P]),
     "hcp_concat2_bf16": (I, [P, I, P, I, P, L, I, P]),
     "hcp_silu_fwd": (I, [P, P, L, P]),
@@ -157,7 +161,7 @@ TOOLS_SYMBOLS = tuple(_TOOLS_PROTOTYPES)
 TOOLS_LIB_PATH = Path(__file__).resolve().parent / "libhcp_mi355x_tools.so"
 
 
-ABI_VERSION = 7         # include/hcp_mi355x.h HCP_ABI_VERSION: bumped whenever an exported signature or descriptor layout changes
+ABI_VERSION = 8         # include/hcp_mi355x.h HCP_ABI_VERSION: bumped whenever an exported signature or descriptor layout changes
 
 
 class HcpError(RuntimeError):

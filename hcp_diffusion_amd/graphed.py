@@ -13,8 +13,9 @@ What trains may be LoRA blocks (their flat `LoraBucket`), host parameters (full 
 is unaffected), or both.  Every trainable parameter is an INPUT of the autograd node: the engine then runs each parameter's
 AccumulateGrad node after the backward graph was enqueued (with an undefined gradient — the kernels already wrote `.grad`), which is
 what torch DDP's reducer hooks hang on; stock DDP therefore averages the bucket views exactly as it does for the eager module
-(tests/test_dist.py).  Falls back to the eager path, per call, when the call is not capturable: no grad mode, LoRA dropout active,
-forward hooks on the module (ControlNet's feeder / branch hooks run per-step Python).
+(tests/test_dist.py).  Falls back to the eager path, per call, when the call is not capturable: no grad mode, LoRA dropout active through
+torch's op (native dropout — `module.enable_native_dropout(seed)`, csrc/dropout.hip — is captured: its mask is a function of a device
+counter the forward graph itself advances), forward hooks on the module (ControlNet's feeder / branch hooks run per-step Python).
 
 One memory pool is shared by all signatures of a module (one forward/backward pair runs at a time), and at most `MAX_SIGNATURES`
 pairs are kept (least recently used goes first): the reference's aspect-ratio buckets hand a run tens of resolutions.
@@ -76,13 +77,17 @@ def _host_bucket(unet, host_params):
 
 
 def capturable(unet):  # (any native module that holds LoRA layers and / or trainable host parameters: the UNet or the text encoder)
-    """No active dropout, no hooks feeding per-step data, something to train."""
+    """No active torch dropout, no hooks feeding per-step data, something to train."""
     from .lora import LoraBucket, LoraHipLayer
     loose = [m for m in unet.modules() if isinstance(m, LoraHipLayer) and m._bucket is None]
     if loose:                                       # blocks built by the reference's make_hcpdiff: one flat bucket for all of them
         LoraBucket(loose)                           # (the Parameters keep their identity: an optimizer that already holds them is unaffected)
+    nd = getattr(unet, "_hcp_dropout", None)
+    if nd is not None:
+        nd.resolve(unet)
+    native = {id(m.dropout) for m in unet.modules() if isinstance(m, LoraHipLayer) and m._nd is not None}   # these run csrc/dropout.hip
     for m in unet.modules():
-        if isinstance(m, torch.nn.Dropout) and m.p > 0 and m.training:
+        if isinstance(m, torch.nn.Dropout) and m.p > 0 and m.training and id(m) not in native:
             return False
     if unet._forward_pre_hooks or unet._forward_hooks:
         return False
@@ -161,6 +166,8 @@ def capture(unet, inputs, fwd, pool=None):
     e.params = [p for p in unet.parameters() if p.requires_grad]
     e.static_in = [None if t is None else t.detach().clone().requires_grad_(t.requires_grad and t.is_floating_point()) for t in inputs]
     bucket_grads = [bk.grads.detach().clone() for bk in e.buckets] + ([e.host.grads.detach().clone()] if e.host is not None else [])
+    nd = getattr(unet, "_hcp_dropout", None)        # native dropout: the warm-up forwards advance the module's forward count
+    nd_saved = nd.snapshot() if nd is not None else None
     e.wg = ops.WgradContext(grouped=True)           # all LoRA weight gradients of the backward as ONE launch at its end (as NativeTrainer does)
     e.live = None
 
@@ -237,6 +244,8 @@ def capture(unet, inputs, fwd, pool=None):
     # the warm-up and the capture accumulated into the gradient buckets: undo
     for bk, g in zip(list(e.buckets) + ([e.host] if e.host is not None else []), bucket_grads):
         bk.grads.copy_(g)
+    if nd is not None:
+        nd.restore(nd_saved)                        # ... put back: the first replay is the module's next forward
     e.pending, e.pending_node = False, None
     return e
 
@@ -277,6 +286,12 @@ def call(unet, inputs, fwd, cache, key):
     # other signature's replay (or a new capture) is free to overwrite.  So while ANY entry awaits its backward, nothing is replayed,
     # captured or evicted: that call runs eagerly (fwd(shape A) -> fwd(shape B) -> backward stays correct).
     if any(_live_pending(x) for x in cache.values()):
+        nd = getattr(unet, "_hcp_dropout", None)
+        if nd is not None and nd.blocks:
+            # an eager forward would advance the device counter the pending backward graph regenerates its masks from
+            raise RuntimeError(f"native dropout of {nd.name}: a second forward before the pending backward would change the masks that "
+                               "backward regenerates — run each backward before the module's next forward, or use torch dropout for "
+                               "this pattern (disable_native_dropout())")
         _warn_once(unet, "pending", "a second forward before the pending backward runs eagerly (hip_graph holds one set of activations)")
         return fwd(*inputs)
     e = cache.get(key)

@@ -538,6 +538,49 @@ def add(a, b):
     return o
 
 
+DROPOUT_MAX_THREADS = 2048 * 256    # csrc/dropout.hip drop_grid: threads of the largest launch (more groups than this: the grid-stride loop turns over)
+
+
+def dropout_state(seed, device):
+    """Device int64[2] = (seed, calls): what the dropout kernels read instead of per-step arguments."""
+    seed = int(seed)
+    if not -(1 << 63) <= seed < (1 << 63):
+        raise ValueError("dropout seed must fit int64")
+    return torch.tensor([seed, 0], dtype=torch.int64, device=device)
+
+
+def _dropout_args(t, state, layer_id, group_base, p):
+    assert t.dtype == BF16 and t.is_contiguous(), "dropout: need contiguous bf16"
+    assert state.dtype == torch.int64 and state.numel() == 2 and state.is_contiguous() and state.device == t.device
+    assert 0 <= int(layer_id) < (1 << 32) and 0 <= int(group_base) < (1 << 64)
+    return int(layer_id), int(group_base), float(p)
+
+
+def dropout_residual_fwd(y, residual, state, layer_id, group_base, p, out=None):
+    """out = keep ? y * scale : 0 (+ residual) with the counter-based mask of csrc/dropout.hip; out=y runs in place."""
+    lid, gb, p = _dropout_args(y, state, layer_id, group_base, p)
+    if residual is not None:
+        assert residual.dtype == BF16 and residual.is_contiguous() and residual.numel() == y.numel()
+    o = torch.empty_like(y) if out is None else out
+    assert o.dtype == BF16 and o.is_contiguous() and o.numel() == y.numel()
+    _chk(lib().hcp_dropout_residual_fwd(_p(y), _p(residual), _p(o), y.numel(), _p(state), lid, gb, p, _stream(y)), "hcp_dropout_residual_fwd")
+    return o
+
+
+def dropout_bwd(dy, state, layer_id, group_base, p, out=None):
+    """dx = keep ? dy * scale : 0, the mask regenerated from `state`; out=dy runs in place."""
+    lid, gb, p = _dropout_args(dy, state, layer_id, group_base, p)
+    o = torch.empty_like(dy) if out is None else out
+    assert o.dtype == BF16 and o.is_contiguous() and o.numel() == dy.numel()
+    _chk(lib().hcp_dropout_bwd(_p(dy), _p(o), dy.numel(), _p(state), lid, gb, p, _stream(dy)), "hcp_dropout_bwd")
+    return o
+
+
+def dropout_advance(state):
+    assert state.dtype == torch.int64 and state.numel() == 2 and state.is_contiguous()
+    _chk(lib().hcp_dropout_advance(_p(state), _stream(state)), "hcp_dropout_advance")
+
+
 def concat_channels(a, b):
     """[..., C1] ++ [..., C2] -> [..., C1+C2] (channels-last)."""
     assert a.dtype == BF16 and b.dtype == BF16 and a.is_contiguous() and b.is_contiguous() and a.shape[:-1] == b.shape[:-1]

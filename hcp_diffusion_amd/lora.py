@@ -31,10 +31,11 @@ class LoraHipContainer(PatchPluginContainer):
     def forward(self, x, residual=None, **kwargs):
         return self._run(tuple(self.plugin_names), x, residual, **kwargs)
 
-    def _run(self, names, x, residual=None, drop_block=None, **kwargs):
+    def _run(self, names, x, residual=None, drop_block=None, group_base=0, **kwargs):
         """The host layer with the LoRA blocks `names` (plugin names of this container) applied — all of them for the plain container;
         one branch's for DAPPHipContainer.  drop_block: the block whose dropout acts on the output (default: the last of `names`; the
-        DAPP container hands the container's LAST plugin to BOTH halves, lora_layers_patch.py:132-133)."""
+        DAPP container hands the container's LAST plugin to BOTH halves, lora_layers_patch.py:132-133).  group_base: where this call's
+        elements start in the native dropout mask's counter space (the DAPP container's second half continues after the first)."""
         blocks = [self[n] for n in names]
         b0 = blocks[0]
         if b0.merged or (b0.host_type == "conv" and len(blocks) > 1 and
@@ -44,7 +45,7 @@ class LoraHipContainer(PatchPluginContainer):
             last = drop_block if drop_block is not None else blocks[-1]
             drop = last.dropout.p > 0.0 and last.training
             y = ops.merged_lora_call(self._host, blocks, x, residual=None if drop else residual, **kwargs)
-            return self._dropped(y, last, residual) if drop else y
+            return self._dropped(y, last, residual, group_base) if drop else y
         if len(names) != 1:                            # several blocks on one host: their rank slots side by side
             multi = self._multis.get(names) if self._multis else None
             if multi is None:
@@ -57,11 +58,11 @@ class LoraHipContainer(PatchPluginContainer):
                 host = self._host
                 y = ops.conv3x3(x, host, x2=kwargs.pop("x2", None), rowbias=kwargs.pop("rowbias", None), residual=None if drop else residual,
                                 stride=host.stride[0], upsample=kwargs.pop("upsample", False), lora=multi, **kwargs)
-                return self._dropped(y, last, residual) if drop else y
+                return self._dropped(y, last, residual, group_base) if drop else y
             if kwargs:
                 raise NotImplementedError(f"LoraHipContainer: unsupported call arguments {list(kwargs)}")
             if drop:
-                return self._dropped(ops.linear(x, self._host, multi, None), last, residual)
+                return self._dropped(ops.linear(x, self._host, multi, None), last, residual, group_base)
             return ops.linear(x, self._host, multi, residual)
         blk = blocks[0]
         dblk = drop_block if drop_block is not None else blk
@@ -70,18 +71,23 @@ class LoraHipContainer(PatchPluginContainer):
             host = self._host
             y = ops.conv3x3(x, host, x2=kwargs.pop("x2", None), rowbias=kwargs.pop("rowbias", None), residual=None if drop else residual,
                             stride=host.stride[0], upsample=kwargs.pop("upsample", False), lora=blk, **kwargs)
-            return self._dropped(y, dblk, residual) if drop else y
+            return self._dropped(y, dblk, residual, group_base) if drop else y
         if kwargs:
             raise NotImplementedError(f"LoraHipContainer: unsupported call arguments {list(kwargs)}")
         if drop:
-            return self._dropped(ops.linear(x, self._host, blk, None), dblk, residual)
+            return self._dropped(ops.linear(x, self._host, blk, None), dblk, residual, group_base)
         return ops.linear(x, self._host, blk, residual)
 
     @staticmethod
-    def _dropped(y, blk, residual):
+    def _dropped(y, blk, residual, group_base=0):
         """``dropout(layer(x, W_host + dW, bias))`` (lora_base_patch.py:74): the reference drops the WHOLE layer output, host path
         included, with torch's dropout (its Philox stream, its 1/(1-p) scaling) — reproduced with the same op; a residual that
-        the native caller wanted fused into the GEMM epilogue is added afterwards (it is not part of the layer's output)."""
+        the native caller wanted fused into the GEMM epilogue is added afterwards (it is not part of the layer's output).
+        With native dropout switched on for the owning top-level module (dropout.NativeDropoutMixin.enable_native_dropout; the block
+        then carries its layer id): ONE kernel, mask and residual add together, nothing stored for the backward (csrc/dropout.hip)."""
+        nd = blk._nd
+        if nd is not None:
+            return ops.dropout_residual(y, residual, nd[0].state, nd[1], group_base, blk.dropout.p, nd[0])
         y = blk.dropout(y)
         return y if residual is None else ops.add(y, residual)
 
@@ -133,6 +139,7 @@ class _ConvFactors(nn.Module):
 class LoraHipLayer(PatchPluginBlock):
     container_cls = LoraHipContainer
     wrapable_classes = (nn.Linear, nn.Conv2d)
+    constructed = 0           # blocks ever built (dropout.NativeDropout.resolve: a new block renumbers the layers)
 
     def __init__(self, lora_id, host, rank=1, dropout=0.1, alpha=1.0, bias=False, alpha_auto_scale=True, parent_block=None,
                  host_name=None, **kwargs):
@@ -171,7 +178,17 @@ class LoraHipLayer(PatchPluginBlock):
         self.register_buffer("alpha", torch.tensor(alpha / rank if alpha_auto_scale else alpha, device=host.weight.device))
         self.alpha_f = float(self.alpha)
         self._bucket = None       # set by LoraBucket.adopt
+        self._nd = None           # (dropout.NativeDropout of the owning top-level module, layer id) while native dropout is on
+        LoraHipLayer.constructed += 1
         self._pk = None
+
+    def __getstate__(self):
+        """A copy (copy.deepcopy of a wrapped sub-module: ControlNet copied from a LoRA-wrapped host) or a pickle does not carry the
+        owning module's native-dropout numbering — and with it every block of that module — along: the copy is on torch's dropout until
+        the top-level module that owns IT numbers it."""
+        state = self.__dict__.copy()
+        state["_nd"] = None
+        return state
 
     # ---- reference API surface
     def get_weight(self):
@@ -254,7 +271,8 @@ class DAPPHipContainer(LoraHipContainer):
         # their half of the batch; `upsample` is a flag
         kw = lambda lo: {k: (half(v, lo) if torch.is_tensor(v) else v) for k, v in kwargs.items()}
         y_n = self._run(names["n"], x[:B], half(residual, True), drop_block=last, **kw(True))
-        y_p = self._run(names["p"], x[B:], half(residual, False), drop_block=last, **kw(False))
+        # native dropout: the second half continues the first half's counter space, so the halves get different masks (as two torch calls do)
+        y_p = self._run(names["p"], x[B:], half(residual, False), drop_block=last, group_base=y_n.numel() // 8, **kw(False))
         return torch.cat([y_n, y_p], dim=0)
 
 

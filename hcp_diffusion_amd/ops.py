@@ -709,6 +709,34 @@ class _AddFn(torch.autograd.Function):
 add = _AddFn.apply
 
 
+class _DropoutResidualFn(torch.autograd.Function):
+    """out = dropout(y) (+ residual) with the counter-based mask of csrc/dropout.hip.  Nothing is saved but the reference to `state`: the
+    backward regenerates the mask from (state, layer_id, group_base, p), so `state[1]` must still hold the forward's count when it runs
+    — `guard` (the owning module's dropout.NativeDropout, or None) carries the host-side generation number that checks this."""
+
+    @staticmethod
+    def forward(ctx, y, residual, state, layer_id, group_base, p, guard):
+        ctx.state, ctx.key, ctx.guard = state, (int(layer_id), int(group_base), float(p)), guard
+        ctx.gen = guard.gen if guard is not None else None
+        ctx.shape = y.shape
+        return K.dropout_residual_fwd(y.contiguous(), None if residual is None else residual.contiguous(), state, *ctx.key).view(y.shape)
+
+    @staticmethod
+    def backward(ctx, d):
+        g = ctx.guard
+        if g is not None and g.gen != ctx.gen:
+            raise RuntimeError(f"native dropout of {g.name}: this backward belongs to forward #{ctx.gen} of the module, which has run "
+                               f"{g.gen - ctx.gen} more forward(s) since — the mask is regenerated from the module's forward count, not "
+                               "stored.  Run each backward before the module's next forward, or use torch dropout for this pattern "
+                               "(disable_native_dropout())")
+        dx = K.dropout_bwd(d.contiguous(), ctx.state, *ctx.key).view(ctx.shape) if ctx.needs_input_grad[0] else None
+        return dx, (d if ctx.needs_input_grad[1] else None), None, None, None, None, None
+
+
+def dropout_residual(y, residual, state, layer_id, group_base, p, guard=None):
+    return _DropoutResidualFn.apply(y, residual, state, layer_id, group_base, p, guard)
+
+
 class _ConcatFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):

@@ -27,6 +27,7 @@ from torch import nn
 
 from . import kernels as K
 from . import ops
+from .dropout import NativeDropoutMixin
 from .layers import HipLayerNorm, HipLinear
 
 BF16 = torch.bfloat16
@@ -108,7 +109,8 @@ class _TextTransformer(nn.Module):
         self.final_layer_norm = HipLayerNorm(hidden_size, eps=1e-5)
 
 
-class NativeCLIPTextModel(nn.Module):
+class NativeCLIPTextModel(NativeDropoutMixin, nn.Module):
+    dropout_module_index = 1
     def __init__(self, clip_skip=0, clip_final_norm=True, N_repeats=1, **cfg):
         super().__init__()
         self.config = _Config({**CLIP_L_CONFIG, **_XL_DEFAULTS, **{k: v for k, v in cfg.items() if k in CONFIG_KEYS}})
@@ -137,6 +139,8 @@ class NativeCLIPTextModel(nn.Module):
         (text-encoder LoRA training, lora_conventional.yaml:14-19) replay captured hipGraphs, one pair per input signature."""
         self._hip_graph, self._hip_graphs = bool(on), {}
         self._hcp_capturable = None
+        if getattr(self, "_hcp_dropout", None) is not None:
+            self._hcp_dropout._key = None              # renumber the dropout layers at the next forward
         self.pack_projection()
 
     def forward(self, input_ids, position_ids=None, attention_mask=None, output_hidden_states=None):
@@ -166,6 +170,7 @@ class NativeCLIPTextModel(nn.Module):
         tm = self.text_model
         B, r = input_ids.shape[0], self.N_repeats
         ids_in = input_ids
+        self._native_dropout_begin()                   # native LoRA dropout: this forward's count, before any layer runs
         if r > 1:                                                 # TEEXHook.forward_hook_input (textencoder_ex.py:57-59): 'b (r w) -> (b r) w'
             if input_ids.dim() != 2 or input_ids.shape[1] % r:
                 raise ValueError(f"token ids [B, {r} x L] expected for N_repeats={r}, got {tuple(input_ids.shape)}")
@@ -246,8 +251,10 @@ class NativeCLIPTextModel(nn.Module):
         return self._proj_bf16[1]
 
     @classmethod
-    def from_pretrained(cls, path=None, subfolder="text_encoder", device="cuda", pretrained_model_name_or_path=None, hip_graph=False, **kw):
-        """A diffusers / transformers directory (config.json + model.safetensors) by parameter name (hip_graph: enable_hip_graph())."""
+    def from_pretrained(cls, path=None, subfolder="text_encoder", device="cuda", pretrained_model_name_or_path=None, hip_graph=False,
+                        native_dropout=None, **kw):
+        """A diffusers / transformers directory (config.json + model.safetensors) by parameter name (hip_graph: enable_hip_graph();
+        native_dropout: <seed> = enable_native_dropout(seed))."""
         from safetensors.torch import load_file
         path = path if path is not None else pretrained_model_name_or_path
         root = os.path.join(path, subfolder) if subfolder and os.path.isdir(os.path.join(path, subfolder)) else path
@@ -263,6 +270,8 @@ class NativeCLIPTextModel(nn.Module):
             raise ValueError(f"text-encoder checkpoint lacks {len(missing)} tensors, e.g. {missing[:3]}")
         model.load_state_dict(sd)
         model = model.to(device)
+        if native_dropout is not None:
+            model.enable_native_dropout(native_dropout)
         if hip_graph:
             model.enable_hip_graph()
         return model
@@ -295,6 +304,17 @@ class NativeSDXLTextEncoder(nn.Module):
     def get_input_embeddings(self):
         return [getattr(self, name).get_input_embeddings() for name in self.model_names]
 
+    def enable_native_dropout(self, seed=0):
+        """Forwarded to the children, each with its own state tensor (seed + 1, seed + 2): they are top-level modules of their own."""
+        for i, name in enumerate(self.model_names):
+            getattr(self, name).enable_native_dropout(seed, module_index=1 + i)
+        return self
+
+    def disable_native_dropout(self):
+        for name in self.model_names:
+            getattr(self, name).disable_native_dropout()
+        return self
+
     def enable_hip_graph(self, on=True):
         """Forwarded to the children: clip_B replays captured graphs; clip_bigG (two outputs) stays eager (NativeCLIPTextModel.forward)."""
         for name in self.model_names:
@@ -311,12 +331,14 @@ class NativeSDXLTextEncoder(nn.Module):
         return ops.concat_channels(states[0].contiguous(), states[1].contiguous()), pooled
 
     @classmethod
-    def from_pretrained(cls, path=None, device="cuda", pretrained_model_name_or_path=None, hip_graph=False, **kw):
+    def from_pretrained(cls, path=None, device="cuda", pretrained_model_name_or_path=None, hip_graph=False, native_dropout=None, **kw):
         """A diffusers SDXL directory: ``text_encoder/`` -> clip_B, ``text_encoder_2/`` -> clip_bigG.  kw (clip_skip, clip_final_norm,
         N_repeats) goes to both encoders, as the reference hooks both with one setting."""
         path = path if path is not None else pretrained_model_name_or_path
         pair = cls(NativeCLIPTextModel.from_pretrained(path, subfolder="text_encoder", device=device, **kw),
                    NativeCLIPTextModel.from_pretrained(path, subfolder="text_encoder_2", device=device, **kw))
+        if native_dropout is not None:
+            pair.enable_native_dropout(native_dropout)
         if hip_graph:
             pair.enable_hip_graph()
         return pair

@@ -81,7 +81,7 @@ class NativeTrainer:
                  overlap_wgrad=False, grouped_wgrad=True, train_cfg=None, plugins=None, ema=None, loss_cfg=None, text_encoder=None,
                  lora_te_cfg=None, comm=None, shard_optimizer=None, gradient_accumulation_steps=1, loss_type="eps",
                  overlap_exchange=False, grad_wire="fp32", param_wire="fp32", pt_cfg=None, pt_words=None, pt_weight_decay=5e-4,
-                 optimizer=None, cfg_scale=None, noise_cfg=None):
+                 optimizer=None, cfg_scale=None, noise_cfg=None, native_dropout=None):
         """lora_cfg: the reference's ``lora_unet`` list ({layers, rank, alpha, lr, ...}); train_cfg: its ``unet`` list
         ({layers, lr}) of host modules to fine-tune in full (DreamBooth.yaml:6-10 uses ``layers: ['']`` = everything);
         plugins: [(plugin module, lr)] — trainable hook plugins such as controlnet.ControlNetHipPlugin (make_plugin,
@@ -133,7 +133,10 @@ class NativeTrainer:
         step_size**i)] (one ``randn`` for all levels, in the graph), of which the kernel reads the leading B C hn wn values — one captured
         graph serves every draw.  As in the reference the eps target is the UNNORMALISED pyramid sum, the noisy latents come from the sum
         divided by its std.  Allowed under an active cfg_scale: the noise is made before the repeat.  Zero terminal SNR
-        (alphas_cumprod[T - 1] = 0) is refused with loss_type='sample' and with an SNR-weighted loss_cfg: both divide by it."""
+        (alphas_cumprod[T - 1] = 0) is refused with loss_type='sample' and with an SNR-weighted loss_cfg: both divide by it.
+        native_dropout: None = LoRA dropout through torch's op, today's step bit for bit; a seed = `enable_native_dropout(seed + rank)` on
+        the UNet and the text encoder this trainer owns (csrc/dropout.hip: counter-based mask, nothing stored, the same bits eager and
+        captured).  The mask stream is not part of a checkpoint: a resumed run restarts it."""
         self.noise_pyramid, self.noise_zero_terminal = parse_noise_cfg(noise_cfg)
         if self.noise_zero_terminal:
             if loss_type == "sample":
@@ -223,6 +226,12 @@ class NativeTrainer:
             self.pt_hook = hook
             self._pt_state = _OptState(self.pt_bucket, lr, self.device, segments=self.pt_bucket.segments, weight_decay=pt_weight_decay,
                                        clipped=self.te_bucket is not None, **hyper)
+        self._dropout_modules = []
+        if native_dropout is not None:
+            for mod in (unet, text_encoder):
+                if mod is not None:
+                    mod.enable_native_dropout(int(native_dropout) + self.comm.rank)
+                    self._dropout_modules += [getattr(mod, n) for n in mod.model_names] if hasattr(mod, "model_names") else [mod]
         self._state_list = [st for st in (self._lora_state, *self.host_buckets, self._te_state, self._pt_state) if st is not None]
         self.ema_cfg = None if ema is None else {**dict(decay_max=0.9997, inv_gamma=1.0, power=2.0 / 3.0), **ema}
         if ema is not None:
@@ -615,11 +624,14 @@ class NativeTrainer:
 
     def _snapshot(self):
         snap = [(st, [t.clone() for t in st.tensors()], st.bucket.params.clone(), st.bucket.grads.clone()) for st in self._states()]
-        return snap, torch.get_rng_state(), (torch.cuda.get_rng_state(self.device) if self.device.type == "cuda" else None), random.getstate()
+        drop = [(m._hcp_dropout, m._hcp_dropout.snapshot()) for m in self._dropout_modules if m._hcp_dropout is not None]
+        return snap, torch.get_rng_state(), (torch.cuda.get_rng_state(self.device) if self.device.type == "cuda" else None), random.getstate(), drop
 
     def _restore(self, saved):
-        snap, cpu_rng, dev_rng, host_rng = saved
+        snap, cpu_rng, dev_rng, host_rng, drop = saved
         random.setstate(host_rng)                  # (pyramid noise draws its level sizes from the global `random` module)
+        for nd, saved_nd in drop:                  # native dropout: the warm-up steps advanced the modules' forward counts
+            nd.restore(saved_nd)
         with torch.no_grad():
             for st, ts, p_, g_ in snap:
                 for t, v in zip(st.tensors(), ts):

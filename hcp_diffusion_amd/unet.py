@@ -16,6 +16,7 @@ from torch import nn
 
 from . import kernels as K
 from . import ops
+from .dropout import NativeDropoutMixin
 from .layers import HipConv2d, HipConvIn, HipConvOut, HipGroupNorm, HipLayerNorm, HipLinear
 
 BF16 = torch.bfloat16
@@ -465,7 +466,7 @@ class _Config(dict):
     __getattr__ = dict.__getitem__
 
 
-class NativeUNet2DConditionModel(nn.Module):
+class NativeUNet2DConditionModel(NativeDropoutMixin, nn.Module):
     def __init__(self, **cfg):
         super().__init__()
         cfg = dict(SD15_CONFIG, **cfg)
@@ -508,11 +509,13 @@ class NativeUNet2DConditionModel(nn.Module):
         return cls(**dict(config or {}, **kw))
 
     @classmethod
-    def from_pretrained(cls, path=None, subfolder=None, pretrained_model_name_or_path=None, hip_graph=False, hip_graph_max_signatures=None, **kw):
+    def from_pretrained(cls, path=None, subfolder=None, pretrained_model_name_or_path=None, hip_graph=False, hip_graph_max_signatures=None,
+                        native_dropout=None, **kw):
         """Load diffusers-format weights (config.json + *.safetensors) — names are identical by construction.
         (``pretrained_model_name_or_path``: diffusers' own keyword, as the YAML overlays of cfgs/train/mi355x pass it;
         ``hip_graph: True`` = enable_hip_graph(): the module replays captured graphs under the reference's eager trainer loop;
-        ``hip_graph_max_signatures: N`` = how many aspect-ratio bucket shapes keep their captured pair, default graphed.MAX_SIGNATURES.)"""
+        ``hip_graph_max_signatures: N`` = how many aspect-ratio bucket shapes keep their captured pair, default graphed.MAX_SIGNATURES;
+        ``native_dropout: <seed>`` = enable_native_dropout(seed): LoRA dropout through csrc/dropout.hip, capturable.)"""
         path = path if path is not None else pretrained_model_name_or_path
         import json
         import os
@@ -530,6 +533,8 @@ class NativeUNet2DConditionModel(nn.Module):
                     projection_class_embeddings_input_dim=cfg.get("projection_class_embeddings_input_dim"))
         from safetensors.torch import load_file
         model.load_state_dict(load_file(os.path.join(root, "diffusion_pytorch_model.safetensors")))
+        if native_dropout is not None:
+            model.enable_native_dropout(native_dropout)
         if hip_graph:
             model.enable_hip_graph(max_signatures=hip_graph_max_signatures)
         return model
@@ -628,12 +633,16 @@ class NativeUNet2DConditionModel(nn.Module):
         callables in place of graphs on the interpreter backend."""
         self._hip_graph, self._hip_graphs, self._hip_graph_cpu = bool(on), {}, bool(_recorded_on_cpu)
         self._hcp_capturable = None
+        if getattr(self, "_hcp_dropout", None) is not None:
+            self._hcp_dropout._key = None              # renumber the dropout layers at the next forward
         from . import graphed
         graphed.set_max_signatures(self, max_signatures)
 
     def reset_hip_graph(self):
         self._hip_graphs = {}
         self._hcp_capturable = None
+        if getattr(self, "_hcp_dropout", None) is not None:
+            self._hcp_dropout._key = None              # renumber the dropout layers at the next forward
 
     def forward(self, sample, timestep, encoder_hidden_states, encoder_attention_mask=None, added_cond_kwargs=None,
                 cross_attention_kwargs=None, **kwargs):
@@ -657,6 +666,7 @@ class NativeUNet2DConditionModel(nn.Module):
         if bool(added_cond_kwargs) != text_time:
             raise ValueError("hcp_diffusion_amd: added_cond_kwargs={text_embeds,time_ids} is required by (and only by) a UNet with "
                              "addition_embed_type='text_time' (SDXL; reference models/wrapper.py:66-73)")
+        self._native_dropout_begin()                   # native LoRA dropout: this forward's count, before any layer runs
         if sample.dtype == torch.float16 or encoder_hidden_states.dtype == torch.float16 or \
                 (sample.is_cuda and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.float16):
             # the reference's default mixed_precision (cfgs/train/train_base.yaml:2, train_ac.py:116-123): no fp16 operand packing and no

@@ -32,8 +32,9 @@ int hcp_is_emulated(void); /* 0 for the product library */
  * GEGLU-forward output gact on hcp_gemm_bf16 / hcp_gemm_lora_bf16.  4: prompt tuning — hcp_embedding_pt_fwd_bf16 /
  * hcp_embedding_pt_bwd_f32 (csrc/embedding.hip).  5: folded upsampler convs — hcp_conv_fold_pack / hcp_conv3x3_up_fold_bf16.
  * 6: SDXL's second text encoder — hcp_gelu, hcp_clip_pool_fwd / hcp_clip_pool_bwd.  7: pyramid noise — hcp_pyramid_noise_accum /
- * hcp_pyramid_noise_finish (csrc/noise.hip). */
-#define HCP_ABI_VERSION 7
+ * hcp_pyramid_noise_finish (csrc/noise.hip).  8: native LoRA dropout — hcp_dropout_residual_fwd / hcp_dropout_bwd /
+ * hcp_dropout_advance (csrc/dropout.hip). */
+#define HCP_ABI_VERSION 8
 int hcp_abi_version(void);
 /* Device self-check of the fp32 atomic path (no reference counterpart: the reference's sums are torch's).  workgroups x 256 threads add
  * small integers into line[16] and into bucket[i * stride], i < nb (both cleared here first); exact expected values:
@@ -143,6 +144,18 @@ int hcp_geglu_fwd(const void* h, void* y, long M, int F, hcpStream_t stream);
 int hcp_geglu_bwd(const void* h, const void* dy, void* dh, long M, int F, hcpStream_t stream);
 
 int hcp_add_bf16(const void* a, const void* b, void* out, long n, hcpStream_t stream);
+/* LoRA layer-output dropout (lora_base_patch.py:74) with a counter-based mask that is never stored (csrc/dropout.hip).  state: device
+ * int64[2] = (seed, calls).  A group is 8 consecutive bf16 elements; group g draws Philox4x32-10 with counter (lo32, hi32 of group_base + g,
+ * layer_id, lo32(calls)) and key (lo32, hi32 of seed); element 8g + 2j takes the low 16 bits of output word j, 8g + 2j + 1 the high 16.
+ * keep iff that value >= T = round(p * 65536); survivors are scaled by 1 / (1 - T / 65536) (p >= 1: zeros).
+ * fwd: out = bf16(keep ? y * scale : 0 (+ residual)), fp32 arithmetic, one rounding; residual may be NULL; out may alias y.
+ * bwd: dx = keep ? dy * scale : 0 (the residual's gradient is dy itself); dx may alias dy.  n % 8 == 0, 16-byte aligned buffers.
+ * advance: state[1] += 1 (one launch per training forward of a module, before any of its layers runs). */
+int hcp_dropout_residual_fwd(const void* y, const void* residual, void* out, long n, const long long* state, unsigned layer_id,
+                             unsigned long long group_base, double p, hcpStream_t stream);
+int hcp_dropout_bwd(const void* dy, void* dx, long n, const long long* state, unsigned layer_id, unsigned long long group_base, double p,
+                    hcpStream_t stream);
+int hcp_dropout_advance(long long* state, hcpStream_t stream);
 int hcp_copy2d_bf16(const void* src, int sld, void* dst, int dld, long M, int C, hcpStream_t stream); /* skip concat/split */
 /* torch.cat([h, skip], dim=1) of the up-block ResnetBlock2D and its gradient split in one launch: joint [M][c1+c2] <-> a [M][c1], b [M][c2];
  * split = 0 writes joint, split = 1 writes a and b (c1, c2 multiples of 8). */
