@@ -88,6 +88,12 @@ _PROTOTYPES = {
     # x0, noise, timesteps, alphas_cumprod, xt, partials, std_out, B, C, h, w, stream
     "hcp_pyramid_noise_finish": (I, [P, P, P, P, P, P, P, I, I, I, I, P]),
     "hcp_cfg_ddim_step": (I, [P, P, P, L, I, F, F, F, P]),
+    # x, eps2, x_out, model_in_next, n, B_rows, guided, guidance, table, steps, state, noise, init, noise0, mask, chw, hw, stream
+    "hcp_euler_step": (I, [P, P, P, P, L, I, I, F, P, I, P, P, P, P, P, L, L, P]),
+    # state, table, steps, t_out, rows, stream
+    "hcp_sampler_advance": (I, [P, P, I, P, I, P]),
+    # state, table, steps, x, model_in, n, guided, noise, init, t_out, rows, start_step, stream
+    "hcp_sampler_begin": (I, [P, P, I, P, P, L, I, P, P, P, I, I, P]),
     "hcp_snr_loss_weight": (I, [P, P, P, I, I, F, P]),
     "hcp_quick_gelu": (I, [P, P, P, L, P]),
     "hcp_embedding_bf16": (I, [P, P, P, P, P, L, I, I, P]),
@@ -161,7 +167,7 @@ TOOLS_SYMBOLS = tuple(_TOOLS_PROTOTYPES)
 TOOLS_LIB_PATH = Path(__file__).resolve().parent / "libhcp_mi355x_tools.so"
 
 
-ABI_VERSION = 8         # include/hcp_mi355x.h HCP_ABI_VERSION: bumped whenever an exported signature or descriptor layout changes
+ABI_VERSION = 9         # include/hcp_mi355x.h HCP_ABI_VERSION: bumped whenever an exported signature or descriptor layout changes
 
 
 class HcpError(RuntimeError):

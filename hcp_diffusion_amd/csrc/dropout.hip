@@ -12,6 +12,7 @@
 // Grid-stride over groups, 16-byte loads and stores, no atomics, no workspace; out may alias y (each thread reads its own 16 bytes
 // before it writes them).
 #include "hcp_common.h"
+#include "hcp_philox.h"             // philox4x32_10: shared with sampler.hip
 
 namespace {
 
@@ -22,23 +23,6 @@ inline int drop_grid(long groups) {
     if (g > DROP_MAX_BLOCKS) g = DROP_MAX_BLOCKS;
     if (g < 1) g = 1;
     return (int)g;
-}
-
-HCP_DEVICE uint32_t philox_mulhi(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * (uint64_t)b) >> 32); }
-
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): ten rounds, the key bumped by the Weyl constants
-// between rounds.
-HCP_DEVICE void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
-    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = philox_mulhi(M0, c0), lo0 = M0 * c0;
-        const uint32_t hi1 = philox_mulhi(M1, c2), lo1 = M1 * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += W0; k1 += W1;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
 // out = bf16(keep ? y * scale : 0 (+ res)); res == null: the backward form (y = dy, out = dx)

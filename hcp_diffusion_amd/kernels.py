@@ -730,6 +730,80 @@ def cfg_ddim_step(x, eps2, a_t, a_prev, guidance_scale=1.0, out=None):
     return out
 
 
+SAMPLER_MAX_THREADS = 512 * 256    # csrc/sampler.hip smp_grid: threads of the largest launch (4 elements each; past it the grid-stride loop turns over)
+SAMPLER_ROW = 8                    # floats per step-table row (csrc/sampler.hip)
+
+
+def sampler_state(seed, device):
+    """Device int64[2] = (seed, step): what the sampler kernels read instead of per-step arguments."""
+    seed = int(seed)
+    if not -(1 << 63) <= seed < (1 << 63):
+        raise ValueError("sampler seed must fit int64")
+    return torch.tensor([seed, 0], dtype=torch.int64, device=device)
+
+
+def _sampler_args(table, state, dev):
+    assert table.dtype == torch.float32 and table.dim() == 2 and table.shape[1] == SAMPLER_ROW and table.is_contiguous() and table.device == dev
+    assert state.dtype == torch.int64 and state.numel() == 2 and state.is_contiguous() and state.device == dev
+    return table.shape[0]
+
+
+def _f32c(t, n, name):
+    assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n, f"{name}: need contiguous fp32 of {n} elements"
+    return t
+
+
+def euler_step(x, eps2, table, state, guidance_scale=1.0, noise=None, init=None, noise0=None, mask=None, out=None, model_in_next=None):
+    """One Euler / Euler-ancestral step on row state[1] of `table` (csrc/sampler.hip): eps2 is the UNet output on [uncond ; cond] (2B rows,
+    guided) or on B rows.  noise None: the in-kernel Philox draw.  mask [B,1,h,w] with init and noise0: the legacy inpaint blend.
+    out=x runs in place; model_in_next ([2B,...] when guided, else [B,...]) receives the next UNet input c_in_next * x'."""
+    n = x.numel()
+    steps = _sampler_args(table, state, x.device)
+    _f32c(x, n, "x")
+    guided = eps2.numel() == 2 * n
+    _f32c(eps2, 2 * n if guided else n, "eps2")
+    out = torch.empty_like(x) if out is None else _f32c(out, n, "out")
+    for t, name in ((noise, "noise"), (init, "init"), (noise0, "noise0")):
+        if t is not None:
+            _f32c(t, n, name)
+    if model_in_next is not None:
+        _f32c(model_in_next, 2 * n if guided else n, "model_in_next")
+    B = x.shape[0]
+    chw = n // B
+    hw = chw
+    if mask is not None:
+        hw = mask.numel() // B
+        _f32c(mask, B * hw, "mask")
+    _chk(lib().hcp_euler_step(_p(x), _p(eps2), _p(out), _p(model_in_next), n, B, 1 if guided else 0, float(guidance_scale), _p(table), steps,
+                              _p(state), _p(noise), _p(init), _p(noise0), _p(mask), chw, hw, _stream(x)), "hcp_euler_step")
+    return out
+
+
+def sampler_advance(state, table, t_out):
+    """state[1] <- min(state[1] + 1, steps - 1); t_out (int64) <- the new row's timestep."""
+    steps = _sampler_args(table, state, t_out.device)
+    assert t_out.dtype == torch.int64 and t_out.is_contiguous()
+    _chk(lib().hcp_sampler_advance(_p(state), _p(table), steps, _p(t_out), t_out.numel(), _stream(t_out)), "hcp_sampler_advance")
+
+
+def sampler_begin(state, table, x, t_out, start_step=0, model_in=None, noise=None, init=None):
+    """Start a run at row start_step: state[1], t_out, x <- z * sigma_init (text2img) or init + z * sigma (img2img), in place; z = noise
+    (may be x itself) or, None, drawn in the kernel.  model_in ([2B,...]: guided) receives the first UNet input."""
+    n = x.numel()
+    steps = _sampler_args(table, state, x.device)
+    _f32c(x, n, "x")
+    assert t_out.dtype == torch.int64 and t_out.is_contiguous()
+    guided = model_in is not None and model_in.numel() == 2 * n
+    if model_in is not None:
+        _f32c(model_in, 2 * n if guided else n, "model_in")
+    for t, name in ((noise, "noise"), (init, "init")):
+        if t is not None:
+            _f32c(t, n, name)
+    _chk(lib().hcp_sampler_begin(_p(state), _p(table), steps, _p(x), _p(model_in), n, 1 if guided else 0, _p(noise), _p(init), _p(t_out),
+                                 t_out.numel(), int(start_step), _stream(x)), "hcp_sampler_begin")
+    return x
+
+
 def quick_gelu(x, dy=None):
     """quick_gelu(x) = x * sigmoid(1.702 x) (dy None) or dy * quick_gelu'(x); bf16, any shape with numel % 8 == 0."""
     assert x.dtype == BF16 and x.is_contiguous() and (dy is None or (dy.dtype == BF16 and dy.is_contiguous() and dy.shape == x.shape))

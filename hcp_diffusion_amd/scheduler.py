@@ -246,3 +246,96 @@ class NativeZeroTerminalScheduler(NativeNoiseBase):
         base_scheduler.betas = rescale_zero_terminal_snr(base_scheduler.betas)
         base_scheduler.alphas = 1.0 - base_scheduler.betas
         base_scheduler.alphas_cumprod = torch.cumprod(base_scheduler.alphas, dim=0)
+
+
+class NativeEulerAncestralScheduler:
+    """The method surface of diffusers' EulerAncestralDiscreteScheduler that the reference's pipelines (utils/pipe_hook.py HookPipe_T2I /
+    _I2I / _inpaint) and its ImagePreviewer touch, over csrc/sampler.hip — for a caller that keeps its own denoising loop.
+    ``NativeEulerSampler.sample`` is the same arithmetic with the loop on the device; given the same seed the two agree bit for bit.
+
+    ``step`` is the unguided form of ``hcp_euler_step`` on the row found from ``t``.  The ancestral noise is drawn IN THE KERNEL from
+    (seed, step, element): seeded from ``generator.initial_seed()`` when a generator is given, else from ``seed``.  It is not torch's
+    random stream — the generator's state is neither read nor advanced, and the numbers are not those of diffusers' ``randn_tensor``.
+    'linspace' spacing is refused (non-integer timesteps; sampler.NativeEulerSampler)."""
+    order = 1
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
+                 timestep_spacing="leading", steps_offset=1, prediction_type="epsilon", seed=0, ancestral=True):
+        if beta_schedule != "scaled_linear" or prediction_type != "epsilon":
+            raise NotImplementedError("NativeEulerAncestralScheduler: beta_schedule 'scaled_linear' and prediction_type 'epsilon' exist")
+        from .sampler import NativeEulerSampler
+        self._s = NativeEulerSampler(ancestral, num_train_timesteps, beta_start, beta_end, timestep_spacing, steps_offset, seed)
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, timestep_spacing=timestep_spacing, steps_offset=steps_offset,
+                                      prediction_type=prediction_type)
+        self.alphas_cumprod = self._s.acp
+        self.timesteps = self.sigmas = None
+        self._dev = {}
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        self.num_inference_steps = int(num_inference_steps)
+        self.timesteps = self._s.timesteps(num_inference_steps)        # host int64: the loop's `t` indexes the table without a device read
+        self.sigmas = self._s.sigmas(num_inference_steps)
+        self._table = self._s.table(num_inference_steps)
+        self._rows = {int(t): i for i, t in reversed(list(enumerate(self.timesteps.tolist())))}
+        self._dev = {}
+
+    @property
+    def init_noise_sigma(self):
+        if self.timesteps is None:
+            self.set_timesteps(self.config.num_train_timesteps)
+        return float(self._table[0, 6])
+
+    def _on(self, device):
+        """Per device: the step table, the same rows arranged so that a step is the identity and writes c_in x (scale_model_input),
+        and the (seed, row) state with the host's record of the row it holds."""
+        key = str(device)
+        d = self._dev.get(key)
+        if d is None:
+            scale = self._table.clone()
+            scale[:, 1], scale[:, 2], scale[:, 3] = self._table[:, 0], 0.0, self._table[:, 7]          # sigma_down = sigma, no noise, c_in
+            d = self._dev[key] = dict(table=self._table.to(device), scale=scale.to(device), state=K.sampler_state(self._s.seed, device),
+                                      seed=self._s.seed, row=0, scratch=torch.zeros(1, dtype=torch.int64, device=device))
+        return d
+
+    def _point(self, d, row, seed=None):
+        seed = d["seed"] if seed is None else int(seed)
+        if d["row"] != row or d["seed"] != seed:
+            d["state"].copy_(torch.tensor([seed, row], dtype=torch.int64))
+            d["row"], d["seed"] = row, seed
+
+    def _row(self, t):
+        if self.timesteps is None:
+            raise RuntimeError("set_timesteps() first")
+        t = int(t.reshape(-1)[0]) if torch.is_tensor(t) else int(t)
+        if t not in self._rows:
+            raise ValueError(f"timestep {t} is not one of this run's {self.timesteps.tolist()}")
+        return self._rows[t]
+
+    def scale_model_input(self, sample, timestep):
+        """sample / sqrt(sigma_t^2 + 1), any leading batch (the pipelines hand [2B, ...] when guided)."""
+        x = sample.float().contiguous()
+        d = self._on(x.device)
+        self._point(d, self._row(timestep))
+        out = torch.empty_like(x)
+        K.euler_step(x, x, d["scale"], d["state"], model_in_next=out)            # x' = x + eps * 0, model_in_next = c_in x' 
+        return out.to(sample.dtype)
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True):
+        x, eps = sample.float().contiguous(), model_output.float().contiguous()
+        d = self._on(x.device)
+        row = self._row(timestep)
+        self._point(d, row, generator.initial_seed() if generator is not None else None)
+        prev = K.euler_step(x, eps, d["table"], d["state"]).to(sample.dtype)
+        K.sampler_advance(d["state"], d["table"], d["scratch"])            # the next step's row, without a host write
+        d["row"] = min(row + 1, self._table.shape[0] - 1)
+        return SimpleNamespace(prev_sample=prev) if return_dict else (prev,)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """Sigma space: original + noise * sigma_t (one timestep for the whole batch, as the pipelines call it)."""
+        x0 = original_samples.float().contiguous()
+        d = self._on(x0.device)
+        out = noise.float().contiguous().clone()
+        K.sampler_begin(d["state"], d["table"], out, d["scratch"], self._row(timesteps), noise=out, init=x0)
+        d["row"] = self._row(timesteps)                                     # hcp_sampler_begin set state[1] to that row
+        return out.to(original_samples.dtype)

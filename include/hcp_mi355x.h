@@ -33,8 +33,9 @@ int hcp_is_emulated(void); /* 0 for the product library */
  * hcp_embedding_pt_bwd_f32 (csrc/embedding.hip).  5: folded upsampler convs — hcp_conv_fold_pack / hcp_conv3x3_up_fold_bf16.
  * 6: SDXL's second text encoder — hcp_gelu, hcp_clip_pool_fwd / hcp_clip_pool_bwd.  7: pyramid noise — hcp_pyramid_noise_accum /
  * hcp_pyramid_noise_finish (csrc/noise.hip).  8: native LoRA dropout — hcp_dropout_residual_fwd / hcp_dropout_bwd /
- * hcp_dropout_advance (csrc/dropout.hip). */
-#define HCP_ABI_VERSION 8
+ * hcp_dropout_advance (csrc/dropout.hip).  9: Euler / Euler-ancestral sampler — hcp_euler_step / hcp_sampler_advance /
+ * hcp_sampler_begin (csrc/sampler.hip). */
+#define HCP_ABI_VERSION 9
 int hcp_abi_version(void);
 /* Device self-check of the fp32 atomic path (no reference counterpart: the reference's sums are torch's).  workgroups x 256 threads add
  * small integers into line[16] and into bucket[i * stride], i < nb (both cleared here first); exact expected values:
@@ -361,6 +362,28 @@ int hcp_cast_bf16_f32(const void* src_bf16, float* dst, long n, hcpStream_t stre
  * out = sqrt(a_prev) (x - sqrt(1 - a_t) eps) / sqrt(a_t) + sqrt(1 - a_prev) eps.  fp32, out may alias x. */
 int hcp_cfg_ddim_step(const float* x, const float* eps2, float* out, long n, int guided, float guidance_scale,
                       float alpha_cumprod_t, float alpha_cumprod_prev, hcpStream_t stream);
+
+/* Euler / Euler-ancestral sampling (diffusers EulerAncestralDiscreteScheduler / EulerDiscreteScheduler, epsilon prediction) with
+ * classifier-free guidance, the legacy inpaint blend (utils/pipe_hook.py:429,442,453) and the next UNet input fused in (csrc/sampler.hip).
+ * table: device float[steps][8], row i = (sigma_i, sigma_down_i, sigma_up_i, c_in_next_i, timestep_i, timestep_next_i, sigma_init_i,
+ * c_in_i) with c_in = 1 / sqrt(sigma^2 + 1) and sigma_init the scale of a text2img start at row i; the final row of a run has
+ * sigma_down = sigma_up = 0, c_in_next = 1 (sigma_down == 0 marks it).  state: device int64[2] = (seed, step); the kernels read row
+ * state[1], clamped into the table, so no per-step value is an argument and one captured graph serves every step.
+ * step:    eps = eps2[:n] + guidance (eps2[n:] - eps2[:n]) when guided, else eps2[:n];  x' = x + eps (sigma_down - sigma) + z sigma_up with
+ *          z = noise[i], or (noise NULL) Box-Muller of Philox4x32-10 on counter (lo32, hi32 of i / 4, lo32(step), 0x53414D50), key (lo32,
+ *          hi32 of seed), u = (w + 0.5) 2^-32, (z0, z1) = sqrt(-2 ln u0) (cos, sin)(2 pi u1), (z2, z3) from (u2, u3); nothing drawn when
+ *          sigma_up == 0.  mask [B_rows,1,h,w] (hw = h w, chw = channels hw; needs init and noise0): x' = m (init + sigma noise0) +
+ *          (1 - m) x', on the final row m init + (1 - m) x'.  x_out = x' (may alias x); model_in_next (nullable) [i] and, guided,
+ *          [n + i] = c_in_next x'.  n % 4 == 0, 16-byte aligned fp32 buffers.
+ * advance: state[1] <- min(state[1] + 1, steps - 1), t_out[0..rows) <- timestep of the new row (its own launch, after the step).
+ * begin:   state[1] <- start_step, t_out <- its timestep, x <- z sigma_init (init NULL) or init + z sigma, z = noise[i] (may be x) or the
+ *          draw with step word 0xFFFFFFFF; model_in (nullable) [i] and, guided, [n + i] = c_in x. */
+int hcp_euler_step(const float* x, const float* eps2, float* x_out, float* model_in_next, long n, int B_rows, int guided, float guidance,
+                   const float* table, int steps, const long long* state, const float* noise, const float* init, const float* noise0,
+                   const float* mask, long chw, long hw, hcpStream_t stream);
+int hcp_sampler_advance(long long* state, const float* table, int steps, long long* t_out, int rows, hcpStream_t stream);
+int hcp_sampler_begin(long long* state, const float* table, int steps, float* x, float* model_in, long n, int guided, const float* noise,
+                      const float* init, long long* t_out, int rows, int start_step, hcpStream_t stream);
 
 /* (the tuning / ablation hooks of the -DHCP_TOOLS build are declared in include/hcp_mi355x_tools.h: they are not part of this ABI) */
 
